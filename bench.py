@@ -23,12 +23,18 @@ the timed workload with --weak.  `--dry` prints the plan of such a job (partitio
 N = 2, 4, 8 without touching a device.  `--replicas` runs one independent volume per rank instead; `--loopback R` runs
 R slab ranks on ONE GPU (diagnostic).
 
-One JSON line on stdout (rank 0).  Besides the driver's contract it carries
+One JSON line on stdout (rank 0).  At N = 1 a plain run sets up, warms up, times the --steps steps and prints the line
+(metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of one timed step); nothing else runs.  With --full
+the line also carries what is measured outside the timed steps:
+  config.*      detect / describe split, matcher, descriptor-kernel statistics, kpSift3D program, host-buffer API,
+                dense 256^3, anisotropic, two-volume and off-grid configurations (--no-match leaves them out)
   roofline      the fused X+Y Gaussian kernel at 512^3 (dominant kernel of the north-star Gaussian),
                 timed with HIP events on the stream it is launched on; per-width application
-                numbers ride along in config.gauss_apps.
+                numbers ride along in config.gauss_apps (--no-roofline leaves it out).
   cpu_baseline  the unmodified reference (oracle/_ref, kind "reference") or, if that is not
-                available, the oracle port -- timed on this box's host cores on a bounded sample.
+                available, the oracle port -- timed on this box's host cores on a bounded sample (--no-cpu-baseline).
+--dump-outputs DIR (N = 1) writes what the last timed step returned -- keypoints, rotations and a fixed sample of the
+descriptors -- as DIR/*.npy (dump_outputs); the inputs depend on the arguments only, so two builds compare file by file.
 """
 from __future__ import annotations
 
@@ -175,6 +181,41 @@ def kp_digest(kp):
         return 0, hashlib.sha256(b"").hexdigest()
     raw = np.ctypeslib.as_array(C.cast(kp.buf, C.POINTER(C.c_uint8)), shape=(K, C.sizeof(abi.Keypoint)))
     return K, hashlib.sha256(np.ascontiguousarray(raw[:, 72:112]).tobytes() + np.ascontiguousarray(raw[:, 0:36]).tobytes()).hexdigest()
+
+
+DUMP_BYTES = 60_000_000                             # --dump-outputs writes at most this much (the contract allows 64 MB)
+
+
+def dump_outputs(out_dir, dev, kp, d_desc):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in out_dir.
+      keypoints.npy            float64 [K, 6]   x, y, z, sd, octave, level of every keypoint, in list order
+      keypoint_rotations.npy   float32 [K, 9]   the rotation matrix of every keypoint (row-major)
+      descriptor_rows.npy      float64 [M]      which keypoints the descriptor sample holds (a seeded draw, sorted)
+      descriptors.npy          float32 [M, 768] their histogram bins (the device records' xd..sd tail is not filled on this path)
+    M = K where everything fits in DUMP_BYTES, else as many rows as fit, drawn with numpy seed 0 (the same rows for the same K)."""
+    os.makedirs(out_dir, exist_ok=True)
+    K = int(kp.slab.num)
+    sz = C.sizeof(abi.Keypoint)
+    raw = (np.ctypeslib.as_array(C.cast(kp.buf, C.POINTER(C.c_uint8)), shape=(K, sz)).copy() if K
+           else np.zeros((0, sz), np.uint8))
+
+    def field(name, ctype, count=1):
+        off = getattr(abi.Keypoint, name).offset
+        return np.ascontiguousarray(raw[:, off:off + count * C.sizeof(ctype)]).view(np.dtype(ctype)).reshape(K, count)
+
+    kps = np.concatenate([field("xd", C.c_double), field("yd", C.c_double), field("zd", C.c_double), field("sd", C.c_double),
+                          field("o", C.c_int).astype(np.float64), field("s", C.c_int).astype(np.float64)], axis=1)
+    np.save(os.path.join(out_dir, "keypoints.npy"), kps)
+    np.save(os.path.join(out_dir, "keypoint_rotations.npy"), field("r_data", C.c_float, 9))
+    per_row = abi.DESC_NUMEL * 4 + 8                                   # bins + the row index
+    fit = max(0, DUMP_BYTES - kps.nbytes - 36 * K) // per_row
+    rows = np.arange(K) if K <= fit else np.sort(np.random.default_rng(0).choice(K, size=fit, replace=False))
+    rec = dev.download(d_desc.value, (K, C.sizeof(abi.SIFT3D_Descriptor) // 4), np.float32) if K else \
+        np.zeros((0, C.sizeof(abi.SIFT3D_Descriptor) // 4), np.float32)
+    rec = rec[rows]
+    np.save(os.path.join(out_dir, "descriptor_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "descriptors.npy"), np.ascontiguousarray(rec[:, :abi.DESC_NUMEL]))
+    log(f"bench.py: wrote {K} keypoints and {len(rows)} descriptors to {out_dir}")
 
 
 def single_gpu_digest(L, dev, dims, nblobs):
@@ -912,6 +953,13 @@ def main():
                     help="diagnostic on one GPU: R Z-slab ranks as host threads sharing the device (loop-back transport)")
     ap.add_argument("--replicas", action="store_true",
                     help="N > 1: one independent volume per rank instead of the Z-slab decomposition")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: outside the timed steps also measure the extras (detect / describe split, matcher, descriptor-kernel "
+                         "statistics, kpSift3D program, host-buffer API, dense 256^3, anisotropic, two-volume and off-grid "
+                         "configurations, Gaussian roofline, CPU baseline); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the last timed step computed to DIR/*.npy (keypoints, rotations, a fixed sample of "
+                         "the descriptors)")
     args = ap.parse_args()
 
     if args.dry:
@@ -923,6 +971,9 @@ def main():
     launched = "WORLD_SIZE" in os.environ                       # under torchrun: one process per rank
     if launched and world != args.gpus:
         log(f"bench.py: WORLD_SIZE={world} but --gpus {args.gpus}: refusing to report a number for a different GPU count")
+        raise SystemExit(2)
+    if args.dump_outputs and (world > 1 or args.gpus > 1 or args.loopback > 1 or os.environ.get("S3D_BENCH_FORCE_SLAB")):
+        log("bench.py: --dump-outputs is implemented for the single-GPU workload only")
         raise SystemExit(2)
     dist = None
     if world > 1 or args.gpus > 1:
@@ -989,9 +1040,10 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # split timing of three extra untimed steps (detect vs describe; the smaller of each: a single shot picks up host jitter), for the record
+    # --full: split timing of three extra untimed steps (detect vs describe; the smaller of each: a single shot picks up host
+    # jitter), for the record
     t_detect = t_describe = float("inf")
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         full_sync()
         t0 = time.perf_counter()
         lib.sift.sift3d_amd_detect_keypoints_dev(C.byref(s), C.c_void_p(d_vol), n, n, n, 1.0, 1.0, 1.0, C.byref(kp))
@@ -1016,6 +1068,8 @@ def main():
         elapsed = float(t.item())
     K = int(kp.slab.num)
     ncand = int(lib.sift.sift3d_amd_last_num_candidates(C.byref(s)))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dev, kp, d_desc)
 
     result = None
     if rank == 0:
@@ -1029,10 +1083,10 @@ def main():
             "config": {"workload": f"{n}^3 float32 blobs+noise ({nblobs} blobs, seed=rank), unit voxels, default SIFT3D "
                                    f"parameters; detect + describe all keypoints, input and descriptors resident in HBM",
                        "keypoints": K, "extrema_candidates": ncand,
-                       "detect_ms": round(t_detect * 1e3, 3), "describe_ms": round(t_describe * 1e3, 3),
+                       **({"detect_ms": round(t_detect * 1e3, 3), "describe_ms": round(t_describe * 1e3, 3)} if args.full else {}),
                        "parallelism": "1 volume per GPU (weak), no data-path collective" if world > 1 else "1 GPU"},
         }
-    if rank == 0 and K and not args.no_match:
+    if rank == 0 and K and args.full and not args.no_match:
         # row f1, outside the timed region: SIFT3D_nn_match of this volume's K descriptors against themselves
         # (device resident; the cost does not depend on the data: 2 exhaustive K x K f64 SSD passes)
         # The first call of a process allocates the matcher's device scratch (4.3 bytes per pair: 4 GB here; 10-130 ms
@@ -1050,7 +1104,7 @@ def main():
                                      "Gpairs_per_s": round(2.0 * K * K / t_match / 1e9, 1),
                                      "method": "f32 screening of all pairs (forward and backward pass) + exact f64 verification "
                                                "of the candidates; indices bit-identical to the exhaustive f64 search"}
-    if rank == 0 and K and not args.no_match:
+    if rank == 0 and K and args.full and not args.no_match:
         # what the descriptor kernel (65 % of the step) works through, outside the timed region: the kernel's counting
         # instantiation returns the number of accepted window voxels per keypoint
         lib.sift.sift3d_amd_describe_window_stats.argtypes = [C.POINTER(abi.SIFT3D), C.POINTER(abi.Keypoint_store),
@@ -1076,7 +1130,7 @@ def main():
                      "conflict-free ds_add_u32 per voxel into 16 bank-private copies of 32-bit fields, 4.2 clk per wave and CU: "
                      "lds_data_path_floor_ms) and the per-keypoint fixed work run under it (two 512-thread workgroups per CU); not "
                      "HBM, not MFMA -- DESIGN.md section 4, profiles/r04_describe_field32.txt"}
-    if rank == 0 and not args.no_match:
+    if rank == 0 and args.full and not args.no_match:
         # BASELINE configs[0] flavour, outside the timed region: the kpSift3D program on a 128^3 NIfTI-1 volume
         # (.nii.gz in, keypoint and descriptor CSVs out) -- process start, HIP initialisation, zlib and CSV
         # formatting included: plumbing, not throughput.
@@ -1098,7 +1152,7 @@ def main():
                     result["config"]["kpSift3D_128"] = {"wall_ms": round(t_cli * 1e3, 1), "keypoints": nk,
                                                         "returncode": r.returncode}
                 lib.free_image(him)
-    if rank == 0 and not args.no_match:
+    if rank == 0 and args.full and not args.no_match:
         # SURVEY 8(d) "API-to-API", outside the timed region: the same volume through the reference's own entry points
         # with HOST buffers (pageable Image in, host Keypoint_store / SIFT3D_Descriptor_store out): what a relinked
         # caller sees, PCIe transfers included.  Never `value`.
@@ -1137,7 +1191,7 @@ def main():
         lib.sift.cleanup_Keypoint_store(C.byref(hkp))
         lib.free_image(him)
         lib.sift.cleanup_SIFT3D(C.byref(hs))
-    if rank == 0 and not args.no_match:
+    if rank == 0 and args.full and not args.no_match:
         # BASELINE configs[2], outside the timed region: SIFT3D_extract_dense_descriptors on a 256^3 volume,
         # device to device (12-channel output, 805 MB)
         nd = 256
@@ -1163,7 +1217,7 @@ def main():
         dev.free(d_in)
         dev.free(d_out)
         lib.sift.cleanup_SIFT3D(C.byref(s2))
-    if rank == 0 and not args.no_match:
+    if rank == 0 and args.full and not args.no_match:
         # BASELINE configs[4] flavour, outside the timed region: the same volume read as anisotropic slices
         # (units 1 x 1 x 1.5): in-plane passes on the fused kernel, the z pass on the generic one
         s3 = abi.SIFT3D()
@@ -1214,7 +1268,7 @@ def main():
             dev.free(d_vol2)
             lib.sift.cleanup_SIFT3D(C.byref(s4))
         lib.sift.cleanup_SIFT3D(C.byref(s3))
-    if rank == 0 and not args.no_match:
+    if rank == 0 and args.full and not args.no_match:
         # Off the unit-voxel, multiple-of-four grid (outside the timed region): a 0.7 x 0.7 x 1.5 mm volume (clinical CT
         # spacing: taps 1.43 voxels apart in plane, 2/3 along z -- every pass table-driven, s3d_gauss_tab.hip) and a volume
         # whose rows are 511 voxels long.  ratio_to_unit = detect time per voxel over the unit-voxel 512^3 detect of this run.
@@ -1250,9 +1304,9 @@ def main():
             dev.free(d_e)
             lib.sift.cleanup_Keypoint_store(C.byref(kpe))
             lib.sift.cleanup_SIFT3D(C.byref(se))
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         add_roofline(result, dev, n)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline()
         except Exception as e:            # the baseline is a report, never a reason to lose the GPU number

@@ -27,7 +27,7 @@ def build(ref: bool = True) -> None:
     is not using it."""
     subprocess.run(["make", "-s", "-C", HERE, "port"], check=True)
     if ref and os.path.isdir("/root/reference/imutil"):
-        subprocess.run(["make", "-s", "-C", HERE, "ref"], check=True)
+        subprocess.run(["make", "-s", "-C", HERE, "ref", "examples"], check=True)
 
 
 def have_ref() -> bool:

@@ -1,9 +1,9 @@
 """Source-level drop-in check: the reference's own example programs (examples/featuresC.c, registerC.c, ioC.c) and its
 command-line programs (cli/kpSift3D.c, denseSift3D.c, regSift3D.c)
-are compiled UNCHANGED, from where they lie under /root/reference, against include/compat/*.h and
-libsift3d_amd.so, and run (device work on the SIMT emulator build, interposed with LD_PRELOAD) on synthetic
-volumes placed under the file names the examples hard-code.  Skipped where the reference tree is absent
-(the GPU box); nothing of the reference is copied into this repository.
+are compiled UNCHANGED by build() (oracle/Makefile, target `examples`) into oracle/_ref/bin, against include/compat/*.h and
+libsift3d_amd.so, and run here (device work on the SIMT emulator build, interposed with LD_PRELOAD) on synthetic
+volumes placed under the file names the examples hard-code.  Skipped where oracle/_ref/bin was not built (no reference
+sources where build() ran); nothing of the reference is copied into this repository.
 """
 import gzip
 import os
@@ -17,26 +17,18 @@ from tests.test_cli import _csv, _dense_end_to_end, _kp_end_to_end, _nii_f32
 from tests.test_host_io import nifti1_bytes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXAMPLES = "/root/reference/examples"
-REF_CLI = "/root/reference/cli"
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "bin")
 EMU = os.path.join(ROOT, "tests", "emu")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="reference tree not present")
+pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF_BIN, "regSift3D")),
+                                reason="oracle/_ref/bin not built (reference sources not present where build() ran)")
 
 
 @pytest.fixture(scope="module")
-def built(tmp_path_factory):
+def built():
     _b.build()
     subprocess.run(["sh", os.path.join(EMU, "build_emu.sh")], check=True, capture_output=True)
-    out = tmp_path_factory.mktemp("examples")
-    exes = {}
-    for name in ("featuresC", "registerC", "ioC"):
-        exe = str(out / name)
-        subprocess.run(["gcc", "-std=gnu11", f"-I{ROOT}/include/compat", os.path.join(EXAMPLES, name + ".c"), "-o", exe,
-                        f"-L{ROOT}/sift3d_amd/lib", "-lsift3d_amd", "-lm", f"-Wl,-rpath,{ROOT}/sift3d_amd/lib"],
-                       check=True, capture_output=True)
-        exes[name] = exe
-    return exes
+    return {name: os.path.join(REF_BIN, name) for name in ("featuresC", "registerC", "ioC")}
 
 
 def _run(exe, cwd):
@@ -87,20 +79,12 @@ def test_registerC(built, tmp_path):
 
 
 @pytest.fixture(scope="module")
-def ref_cli(tmp_path_factory):
+def ref_cli():
     """cli/*.c of the reference, as they lie, against include/compat + libsift3d_amd.so (row f3/f4: "the reference's
     command lines").  regSift3D links the three exported defaults (cli/regSift3D.c:83-84)."""
     _b.build()
     subprocess.run(["sh", os.path.join(EMU, "build_emu.sh")], check=True, capture_output=True)
-    out = tmp_path_factory.mktemp("refcli")
-    exes = {}
-    for name in ("kpSift3D", "denseSift3D", "regSift3D"):
-        exe = str(out / name)
-        subprocess.run(["gcc", "-std=gnu11", "-w", f"-I{ROOT}/include/compat", os.path.join(REF_CLI, name + ".c"), "-o", exe,
-                        f"-L{ROOT}/sift3d_amd/lib", "-lsift3d_amd", "-lm", f"-Wl,-rpath,{ROOT}/sift3d_amd/lib"],
-                       check=True, capture_output=True)
-        exes[name] = exe
-    return exes
+    return {name: os.path.join(REF_BIN, name) for name in ("kpSift3D", "denseSift3D", "regSift3D")}
 
 
 def test_reference_regSift3D_help_prints_the_exported_defaults(ref_cli):
