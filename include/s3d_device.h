@@ -33,6 +33,7 @@ int s3d_rt_device_count(int *count);
 int s3d_rt_set_device(int dev);
 int s3d_rt_get_device(int *dev);
 int s3d_rt_malloc(void **d_ptr, size_t bytes);
+int s3d_rt_mem_info(size_t *free_bytes, size_t *total_bytes);   /* hipMemGetInfo of the current device */
 int s3d_rt_free(void *d_ptr);
 int s3d_rt_h2d(void *d_dst, const void *src, size_t bytes, s3d_stream stream);
 int s3d_rt_d2h(void *dst, const void *d_src, size_t bytes, s3d_stream stream);

@@ -726,7 +726,9 @@ extern "C" int s3d_k_dense_bary_blur(const float *d_smooth, float *d_dst, float 
     hipStream_t st = (hipStream_t)stream;
     S3dTaps t;
     if (!s3d_k_fast_mc_eligible(nx, ny, nz, S3D_NVERT, uf, width) || ny > 65535) return 1;
-    if ((size_t)nx * ny >= 0x7fffffffu / 3) return 1;
+    /* the z pass addresses its 3 nx ny float4 columns with the 32-bit byte offset loff = colid * 16 (k_dmarch): it wraps once
+     * 48 nx ny exceeds 2^32 (nx ny >= 89 478 486) -- such planes take the separate steps, which address in 64 bits */
+    if ((size_t)nx * ny * 48u > 0xffffffffull) return 1;
     if (check_taps(taps, width, &t)) return S3D_ERR;
     switch (width / 2) {
     case 1: return launch_bary_blur<1>(d_smooth, d_dst, d_tmp, nx, ny, nz, unitsf, d_mesh, t, d_post_in, st);

@@ -1053,6 +1053,9 @@ static int launch_fast(const float *d_src, float *d_dst, float *d_tmp, int nx, i
     const unsigned ncy = s3d_div_up(ny, cy), ncz = s3d_div_up(nzo, cz);
     const size_t plane = (size_t)nx * ny;
     if (ncy > 65535 || (unsigned)(zb - za) > 65535u) S3D_FAIL("volume too large for the fast-path grid");
+    /* k_gauss_zs addresses a plane with the 32-bit byte offset loff = colid * 16: planes of 4 GiB and more go to k_gauss_z */
+    const bool zs_ok = (size_t)(nx / 4) * ny * 16u < 0xffffffffull;
+    if (d_maxout && ((nx & 3) || !zs_ok)) S3D_FAIL("maximum-keeping z pass: ragged rows or a plane of 4 GiB or more");
     if (g_ev[0]) S3D_HIP(hipEventRecord(g_ev[0], st));
     const bool ragged = nx % 4 != 0;
     const dim3 gxy(s3d_div_up(nx, XY_STRIP), ncy, zb - za);
@@ -1074,7 +1077,7 @@ static int launch_fast(const float *d_src, float *d_dst, float *d_tmp, int nx, i
     else if (d_maxout)
         hipLaunchKernelGGL((k_gauss_zs<HW, 2, true>), dim3(s3d_div_up((size_t)(nx / 4) * ny, 256), ncz), dim3(256), 0, st,
                            d_tmp, d_dst, nx / 4, ny, nz, z0, z1, cz, t, ez, reinterpret_cast<unsigned *>(d_maxout));
-    else if (g_new_z && (size_t)(nx / 4) * ny * 16u < 0xffffffffull)
+    else if (g_new_z && zs_ok)
         hipLaunchKernelGGL((k_gauss_zs<HW, GZ_D, false>), dim3(s3d_div_up((size_t)(nx / 4) * ny, 256), ncz), dim3(256), 0, st,
                            d_tmp, d_dst, nx / 4, ny, nz, z0, z1, cz, t, ez, (unsigned *)nullptr);
     else if (!(g_gauss_mode & 1))
@@ -1515,6 +1518,7 @@ extern "C" int s3d_k_sep_fir_max(const float *d_src, float *d_dst, float *d_tmp,
     if (width < 1 || width > S3D_MAX_TAPS || !(width & 1) || nx < 1 || ny < 1 || nz < 1) return 1;
     if (!fast_eligible(nx, ny, nz, 1, uf, width) || (nx & 3) || d_tmp == d_src || d_tmp == d_dst) return 1;
     if (width / 2 > 8) return 1;                 /* (the widest instantiation of the maximum-keeping z kernel spills registers) */
+    if ((size_t)(nx / 4) * ny * 16u >= 0xffffffffull) return 1;   /* 32-bit plane offsets of k_gauss_zs (launch_fast) */
     if (check_taps(taps, width, &t)) return S3D_ERR;
     S3D_HIP(hipMemsetAsync(d_max, 0, sizeof(float), (hipStream_t)stream));
     return fast_dispatch(d_src, d_dst, d_tmp, nx, ny, nz, 0, nz, width / 2, t, (hipStream_t)stream, nullptr, d_max);

@@ -1,6 +1,7 @@
 /* s3d_rt.hip -- runtime plumbing behind the C-ABI: device memory, copies, streams, events, errors.
  * No compute.  There is deliberately no CPU path: with no HIP device every entry point fails. */
 #include <time.h>
+#include <unistd.h>
 
 #include "s3d_common.h"
 
@@ -27,6 +28,19 @@ extern "C" int s3d_rt_malloc(void **d_ptr, size_t bytes)
     /* 64 bytes of slack: kernels with dword-aligned wide loads (k_describe) may read a few floats past the
      * last element of a volume */
     S3D_HIP(hipMalloc(d_ptr, bytes + 64));
+    return S3D_OK;
+}
+extern "C" int s3d_rt_mem_info(size_t *free_bytes, size_t *total_bytes)
+{
+    *free_bytes = 0;
+    *total_bytes = 0;
+#if defined(S3D_EMU)                                      /* the CPU emulator: device memory is host memory */
+    const size_t pg = (size_t)sysconf(_SC_PAGESIZE);
+    *free_bytes = (size_t)sysconf(_SC_AVPHYS_PAGES) * pg;
+    *total_bytes = (size_t)sysconf(_SC_PHYS_PAGES) * pg;
+#else
+    S3D_HIP(hipMemGetInfo(free_bytes, total_bytes));
+#endif
     return S3D_OK;
 }
 extern "C" int s3d_rt_free(void *d_ptr)

@@ -38,6 +38,7 @@ class DeviceLib:
         L.s3d_rt_device_count.argtypes = [C.POINTER(C.c_int)]
         L.s3d_rt_malloc.argtypes = [C.POINTER(_vp), C.c_size_t]
         L.s3d_rt_free.argtypes = [_vp]
+        L.s3d_rt_mem_info.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.s3d_rt_h2d.argtypes = [_vp, _vp, C.c_size_t, _vp]
         L.s3d_rt_d2h.argtypes = [_vp, _vp, C.c_size_t, _vp]
         L.s3d_rt_d2d.argtypes = [_vp, _vp, C.c_size_t, _vp]
@@ -74,6 +75,12 @@ class DeviceLib:
         n = C.c_int(0)
         rc = self.L.s3d_rt_device_count(C.byref(n))
         return n.value if rc == 0 else 0
+
+    def mem_info(self) -> tuple:
+        """(free, total) bytes of device memory on the current device (hipMemGetInfo)."""
+        free, total = C.c_size_t(0), C.c_size_t(0)
+        self.check(self.L.s3d_rt_mem_info(C.byref(free), C.byref(total)), "s3d_rt_mem_info")
+        return free.value, total.value
 
     # --- memory helpers (numpy <-> HBM) -----------------------------------------------------------
     def malloc(self, nbytes: int) -> int:

@@ -7,6 +7,7 @@ world of one).  Every result must equal the single-GPU entry points bit for bit,
 geometry (1024 slices over 8 ranks: 128-slice slabs, octaves 0-1 sharded, octaves >= 2 replicated) and, with
 S3D_TEST_1024=0 not set, configs[3] itself: one 1024^3 volume, 8 slabs."""
 import ctypes as C
+import json
 import os
 import subprocess
 import sys
@@ -320,8 +321,9 @@ def test_two_processes_share_one_gpu(hip, tmp_path):
 @pytest.mark.skipif(os.environ.get("S3D_TEST_1024") == "0", reason="S3D_TEST_1024=0")
 def test_config3_1024_cubed(hip):
     """BASELINE configs[3]: one 1024^3 float32 volume (4 GiB).  (a) single GPU: 246 249 keypoints -- THIS library's count for
-    the volume of the bench generator (the reference has not been run at this size in the test suite; see DESIGN.md section 2 for
-    what pins it), reference order, orthonormal R, unit-norm descriptors;
+    the volume of the bench generator, reference order, orthonormal R, unit-norm descriptors; positions, scales, octaves and
+    levels byte-equal to the unmodified reference's list, recorded once (tests/golden/ref1024.json: the reference takes
+    ~45 minutes at this size, so it is not run here);
     (b) the same volume as eight 128-slice Z-slabs (loop-back ranks on this GPU): keypoints, R and descriptors
     bit-identical to (a)."""
     import hashlib
@@ -354,6 +356,11 @@ def test_config3_1024_cubed(hip):
     bins = draw[:, :3072].view(np.float32)
     nrm = np.sqrt((bins.astype(np.float64) ** 2).sum(1))
     assert np.abs(nrm - 1).max() < 1e-5 and bins.min() >= 0
+    # positions, scales, octaves and levels against the unmodified reference's run of this volume (tests/golden/ref1024.json)
+    with open(os.path.join(ROOT, "tests", "golden", "ref1024.json")) as f:
+        ref = json.load(f)
+    assert K == ref["keypoints"]
+    assert hashlib.sha256(np.ascontiguousarray(raw[:, 72:112]).tobytes()).hexdigest() == ref["sha256_kp_bytes_72_112"]
     want_kp = hashlib.sha256(np.ascontiguousarray(raw[:, 72:112]).tobytes() + np.ascontiguousarray(raw[:, 0:36]).tobytes()).hexdigest()
     want_desc = hashlib.sha256(np.ascontiguousarray(bins).tobytes()).hexdigest()
     L.cleanup_SIFT3D(C.byref(s))                                               # frees the 37 GB single-GPU pyramid
