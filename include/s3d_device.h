@@ -114,6 +114,29 @@ int s3d_k_sep_fir_slab(const float *d_src, float *d_dst, float *d_tmp, int nx, i
 int s3d_k_sep_fir_div_eligible(int nx, int ny, int nz, const float uf[3], int width);
 int s3d_k_sep_fir_div(const float *d_src, float *d_dst, float *d_tmp, int nx, int ny, int nz, int z0, int z1,
                       const float uf[3], const float *taps, int width, const float *d_div, s3d_stream stream);
+/* ---- volumes of 8- and 16-bit integers, read as stored ---------------------------------------------------------------
+ * Element types by their NIfTI-1 datatype code.  The value of a voxel is (float)((double)raw * slope + inter) everywhere:
+ * two separately rounded f64 operations and one conversion, what the host reader computes (s3d_host_io.c).  d_src must be
+ * aligned to its element size; slope and inter finite. */
+#define S3D_DT_U8 2
+#define S3D_DT_I16 4
+#define S3D_DT_I8 256
+#define S3D_DT_U16 512
+/* bytes per element; 0: not one of the four */
+int s3d_k_typed_elem_size(int dtype);
+/* d_dst[i] = value of d_src[i] (d_dst dword aligned): afterwards the volume is an ordinary float volume */
+int s3d_k_convert_f32(const void *d_src, int dtype, size_t n, double slope, double inter, float *d_dst, s3d_stream stream);
+/* *d_max = max |value of d_src[i]|, the bits s3d_k_absmax gives on the converted volume, from 1 or 2 bytes per voxel.
+ * (The value is monotone in the raw element, roundings included, so the maximum is taken over the raw elements' minimum and
+ * maximum and only those two are converted.) */
+int s3d_k_absmax_typed(const void *d_src, int dtype, size_t n, double slope, double inter, float *d_max, s3d_stream stream);
+/* s3d_k_sep_fir_div over the whole volume with the conversion folded into the loads as well: dst = filter(value(src) / *d_div)
+ * on the fused unit-spacing kernels.  Eligible: where s3d_k_sep_fir_div takes those kernels, nx % 4 == 0, d_src aligned to
+ * four elements and a filter of at most 17 taps; an error otherwise (callers convert first: s3d_k_convert_f32). */
+int s3d_k_sep_fir_div_typed_eligible(const void *d_src, int dtype, int nx, int ny, int nz, const float uf[3], int width);
+int s3d_k_sep_fir_div_typed(const void *d_src, int dtype, double slope, double inter, float *d_dst, float *d_tmp, int nx,
+                            int ny, int nz, const float uf[3], const float *taps, int width, const float *d_div,
+                            s3d_stream stream);
 /* Force a code path (tests / profiling): 0 = auto, 1 = generic per-axis passes, 2 = fused fast path
  * (fails if the configuration is not eligible). */
 /* The three knobs below are per calling thread (thread_local): tests and bench.py set them on the thread that then

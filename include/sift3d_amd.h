@@ -442,6 +442,32 @@ long sift3d_amd_last_num_candidates(const SIFT3D *const sift3d);
 int sift3d_amd_set_stream(SIFT3D *const sift3d, void *hip_stream);
 const char *sift3d_amd_last_error(void);
 
+/* ---- volumes as stored: 8- and 16-bit integers without a float copy ------------------------------------------------------
+ * CT, MR and microscopy volumes are stored as int16, uint16 or uint8.  read_nii widens them to float on the host; the entry
+ * points below keep the stored elements, so the upload is 2 or 1 bytes per voxel instead of 4 and the caller holds no
+ * float copy.  The element types carry their NIfTI-1 datatype codes, so a header's `datatype` can be passed through. */
+enum { SIFT3D_AMD_U8 = 2, SIFT3D_AMD_I16 = 4, SIFT3D_AMD_F32 = 16, SIFT3D_AMD_I8 = 256, SIFT3D_AMD_U16 = 512 };
+/* vol: nx*ny*nz elements of `dtype`, x fastest; on the host (on_device = 0) or in HBM (on_device = 1, read in place, aligned
+ * to its element size).  The result is that of SIFT3D_detect_keypoints on the float image whose voxels are
+ * (float)((double)raw * slope + inter) -- bit for bit: the device evaluates that expression as the host reader does, with
+ * two separately rounded f64 operations, in the loads of the pyramid's first filter where the volume has unit voxels and
+ * whole quads per row (nx % 4 == 0), in a conversion pass of its own otherwise.  slope == 0 counts as 1
+ * (read_nii's rule); slope and inter must be finite.  SIFT3D_AMD_F32 forwards to SIFT3D_detect_keypoints /
+ * sift3d_amd_detect_keypoints_dev (slope and inter must then be 1 and 0).  Afterwards the struct is in the state a float
+ * detect leaves (SIFT3D_extract_descriptors, sift3d_amd_download_pyramid, copy_SIFT3D ...).
+ * With several GPUs (SIFT3D_NGPU > 1 / sift3d_amd_set_num_gpus) the typed transport does not apply: the volume is converted
+ * on the host and takes the float path -- correct, without the saving (and on_device = 1 is then refused). */
+int sift3d_amd_detect_keypoints_typed(SIFT3D *const sift3d, const void *vol, int dtype, int on_device, int nx, int ny, int nz,
+                                      double ux, double uy, double uz, double slope, double inter, Keypoint_store *const kp);
+/* A NIfTI-1 volume (.nii, .nii.gz, .hdr/.img) with its elements as the file stores them: header handling as read_nii (byte
+ * order, vox_offset, units, scl_slope == 0 -> 1).  Single-channel files of the four integer types keep their elements
+ * (byte-swapped where the file is) with the header's slope / inter; every other supported datatype comes back as
+ * SIFT3D_AMD_F32 with slope 1 / inter 0, converted as read_nii converts; files with more than one channel fail.  `data`
+ * is released with sift3d_amd_free_volume. */
+typedef struct { void *data; int dtype; int nx, ny, nz; double ux, uy, uz, slope, inter; } sift3d_amd_volume;
+int sift3d_amd_read_nii_native(const char *path, sift3d_amd_volume *out);
+void sift3d_amd_free_volume(sift3d_amd_volume *v);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

@@ -133,6 +133,47 @@ class Reg_SIFT3D(C.Structure):
                 ("match_ref", Mat_rm), ("nn_thresh", C.c_double), ("verbose", C.c_int)]
 
 
+class Volume(C.Structure):
+    """``sift3d_amd_volume``: a volume with its elements as stored (sift3d_amd_read_nii_native)."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("ux", C.c_double), ("uy", C.c_double), ("uz", C.c_double), ("slope", C.c_double),
+                ("inter", C.c_double)]
+
+
+# element types of the typed entry points: their NIfTI-1 datatype codes (include/sift3d_amd.h)
+SIFT3D_AMD_U8, SIFT3D_AMD_I16, SIFT3D_AMD_F32, SIFT3D_AMD_I8, SIFT3D_AMD_U16 = 2, 4, 16, 256, 512
+TYPED_DTYPES = {np.dtype(np.uint8): SIFT3D_AMD_U8, np.dtype(np.int8): SIFT3D_AMD_I8,
+                np.dtype(np.uint16): SIFT3D_AMD_U16, np.dtype(np.int16): SIFT3D_AMD_I16,
+                np.dtype(np.float32): SIFT3D_AMD_F32}
+
+
+def detect_keypoints_typed(L: C.CDLL, sift3d, vol, kp, units=(1.0, 1.0, 1.0), slope: float = 1.0, inter: float = 0.0,
+                           dtype=None, shape=None) -> int:
+    """sift3d_amd_detect_keypoints_typed on ``vol``: a numpy array [nz, ny, nx] of uint8 / int8 / uint16 / int16 / float32
+    (host form), or a device address -- e.g. ``torch.Tensor.data_ptr()`` -- with ``dtype`` (numpy dtype) and ``shape``
+    (nz, ny, nx) given (device form).  ``L`` must have been through ``device.bind_extensions``.  Returns the C status."""
+    if isinstance(vol, np.ndarray):
+        if vol.dtype not in TYPED_DTYPES:
+            raise TypeError(f"unsupported element type {vol.dtype}")
+        vol = np.ascontiguousarray(vol)
+        nz, ny, nx = vol.shape
+        return L.sift3d_amd_detect_keypoints_typed(C.byref(sift3d), C.c_void_p(vol.ctypes.data), TYPED_DTYPES[vol.dtype], 0,
+                                                   nx, ny, nz, units[0], units[1], units[2], slope, inter, C.byref(kp))
+    if dtype is None or shape is None:
+        raise TypeError("a device address needs dtype and shape")
+    nz, ny, nx = shape
+    return L.sift3d_amd_detect_keypoints_typed(C.byref(sift3d), C.c_void_p(int(vol)), TYPED_DTYPES[np.dtype(dtype)], 1,
+                                               nx, ny, nz, units[0], units[1], units[2], slope, inter, C.byref(kp))
+
+
+def volume_to_numpy(v: Volume) -> np.ndarray:
+    """A copy of a ``Volume``'s elements as [nz, ny, nx] in their stored type."""
+    dt = {code: d for d, code in TYPED_DTYPES.items()}[v.dtype]
+    n = v.nx * v.ny * v.nz
+    buf = (C.c_char * (n * dt.itemsize)).from_address(v.data)
+    return np.frombuffer(buf, dtype=dt).copy().reshape(v.nz, v.ny, v.nx)
+
+
 # (struct, sizeof, {field: offset}) measured on the compiled reference (SURVEY.md section 8b).
 ABI_LAYOUT = [
     (Image, 104, {"data": 0, "cl_image": 8, "s": 16, "size": 24, "nx": 32, "ux": 48, "xs": 72,

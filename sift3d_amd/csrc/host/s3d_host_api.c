@@ -72,6 +72,13 @@ typedef struct {
     int nx, ny, nz, num_octaves, num_levels;
     float *d_im, *d_tmp;
     const float *in_src;    /* input of the pyramid being built: d_im (uploaded) or the caller's device volume */
+    /* ... or a volume of 8- / 16-bit integers as stored (sift3d_amd_detect_keypoints_typed): the caller's device volume, or
+     * d_typed, the staging buffer a host volume is uploaded into (grown like d_im, freed with it) */
+    const void *in_typed;
+    int in_dtype;
+    double in_slope, in_inter;
+    void *d_typed;
+    size_t typed_bytes;
     float *d_level[S3D_MAX_OCTAVES * S3D_MAX_LEVELS];
     size_t level_elems[S3D_MAX_OCTAVES];
     unsigned long long *d_bits;             /* S3D_FUSED_KP_MAX bitmaps of bits_words words */
@@ -186,6 +193,8 @@ static void dfree(void *pp)
 static void ctx_free_pyramid(s3d_ctx *c)
 {
     dfree(&c->d_im); dfree(&c->d_tmp);
+    dfree(&c->d_typed);
+    c->typed_bytes = 0;
     for (int i = 0; i < S3D_MAX_OCTAVES; i++) dfree(&c->d_tmp_oct[i]);
     for (int i = 0; i < S3D_MAX_OCTAVES * S3D_MAX_LEVELS; i++) dfree(&c->d_level[i]);
     dfree(&c->d_bits); dfree(&c->d_scratch);
@@ -564,8 +573,18 @@ static int set_im_meta(SIFT3D *const sift3d, int nx, int ny, int nz, double ux, 
     return SIFT3D_SUCCESS;
 }
 
+/* a volume of 8- or 16-bit integers as stored: element type (SIFT3D_AMD_*), where it lives, and its scaling */
+typedef struct {
+    const void *vol;
+    int dtype, on_device;
+    double slope, inter;
+} s3d_typed_src;
+
+/* `ts` (with host_dense == d_vol == NULL): the input is a typed volume.  Its maximum is taken from the stored elements, and
+ * the first filter reads them too where it can (build_gpyr_dev); the verbatim pass -- reachable through a slope that
+ * overflows to an infinity only -- converts into d_im and goes on as a float volume. */
 static int set_im_device(SIFT3D *const sift3d, const float *host_dense, const float *d_vol, int nx, int ny,
-                         int nz, double ux, double uy, double uz)
+                         int nz, double ux, double uy, double uz, const s3d_typed_src *ts)
 {
     s3d_ctx *c;
     size_t n;
@@ -579,7 +598,30 @@ static int set_im_device(SIFT3D *const sift3d, const float *host_dense, const fl
     n = (size_t)nx * ny * nz;
     /* The maximum now; the division by it rides in the first filter where that is possible (build_gpyr_dev), which then
      * reads a device volume where the caller has it -- no copy, no scaled image. */
-    if (host_dense) {
+    c->in_typed = NULL;
+    if (ts) {
+        const void *d_t = ts->vol;
+        if (!ts->on_device) {                             /* n elements as stored: 1 or 2 bytes per voxel over the bus */
+            const size_t bytes = n * (size_t)s3d_k_typed_elem_size(ts->dtype);
+            if (c->typed_bytes < bytes) {
+                dfree(&c->d_typed);
+                c->typed_bytes = 0;
+                DEV(s3d_rt_malloc(&c->d_typed, bytes));
+                c->typed_bytes = bytes;
+            }
+            DEV(s3d_rt_h2d(c->d_typed, ts->vol, bytes, c->stream));
+            d_t = c->d_typed;
+        }
+        if (c->verbatim) {
+            DEV(s3d_k_convert_f32(d_t, ts->dtype, n, ts->slope, ts->inter, c->d_im, c->stream));
+            c->in_src = c->d_im;
+        } else {
+            c->in_src = NULL;
+            c->in_typed = d_t;
+            c->in_dtype = ts->dtype;
+            c->in_slope = ts->slope; c->in_inter = ts->inter;
+        }
+    } else if (host_dense) {
         DEV(s3d_rt_h2d(c->d_im, host_dense, n * sizeof(float), c->stream));
         c->in_src = c->d_im;
     } else {
@@ -589,7 +631,10 @@ static int set_im_device(SIFT3D *const sift3d, const float *host_dense, const fl
     if (c->verbatim) {
         DEV(s3d_k_seqmax(c->in_src, NULL, n, c->d_red + RED_INMAX, c->d_red + RED_REC, c->stream));
     } else {
-        DEV(s3d_k_absmax(c->in_src, n, c->d_red + RED_INMAX, c->stream));
+        if (c->in_typed)
+            DEV(s3d_k_absmax_typed(c->in_typed, c->in_dtype, n, c->in_slope, c->in_inter, c->d_red + RED_INMAX, c->stream));
+        else
+            DEV(s3d_k_absmax(c->in_src, n, c->d_red + RED_INMAX, c->stream));
         /* ... and on its way home on the copy stream, beside whatever the caller's stream does next: build_gpyr_dev looks at it
          * once the first filter has been enqueued -- the GPU has work queued while the host waits for four bytes -- and sends a
          * volume with a NaN or an infinity to the literal kernels after ONE wasted Gaussian application instead of a wasted
@@ -739,8 +784,26 @@ static int build_gpyr_dev(SIFT3D *const sift3d, s3d_ctx *c, int with_extrema)
         }
     }
     unit_factors(units, 1.0, uf);
-    if (c->in_src == NULL) API_FAIL("sift3d_amd: no input volume");
-    if (!c->verbatim && s3d_k_sep_fir_div_eligible(l0->nx, l0->ny, l0->nz, uf, gss->first_gauss.f.width)) {
+    int first_done = 0;
+    if (c->in_typed) {
+        /* integers as stored (set_im_device; never in the verbatim pass): the first filter converts as it loads where the fused
+         * unit-spacing kernels take whole aligned quads; otherwise one conversion pass into d_im, then exactly the float path */
+        const void *const d_t = c->in_typed;
+        c->in_typed = NULL;
+        if (s3d_k_sep_fir_div_typed_eligible(d_t, c->in_dtype, l0->nx, l0->ny, l0->nz, uf, gss->first_gauss.f.width)) {
+            DEV(s3d_k_sep_fir_div_typed(d_t, c->in_dtype, c->in_slope, c->in_inter, c->d_level[0], c->d_tmp, l0->nx, l0->ny, l0->nz,
+                                        uf, gss->first_gauss.f.kernel, gss->first_gauss.f.width, c->d_red + RED_INMAX, c->stream));
+            first_done = 1;
+        } else {
+            DEV(s3d_k_convert_f32(d_t, c->in_dtype, (size_t)l0->nx * l0->ny * l0->nz, c->in_slope, c->in_inter, c->d_im, c->stream));
+            c->in_src = c->d_im;
+        }
+    }
+    if (first_done) {
+        /* level 0 exists */
+    } else if (c->in_src == NULL) {
+        API_FAIL("sift3d_amd: no input volume");
+    } else if (!c->verbatim && s3d_k_sep_fir_div_eligible(l0->nx, l0->ny, l0->nz, uf, gss->first_gauss.f.width)) {
         DEV(s3d_k_sep_fir_div(c->in_src, c->d_level[0], c->d_tmp, l0->nx, l0->ny, l0->nz, 0, l0->nz, uf,
                               gss->first_gauss.f.kernel, gss->first_gauss.f.width, c->d_red + RED_INMAX, c->stream));
     } else {
@@ -953,7 +1016,7 @@ int sift3d_amd_get_slab_info(const SIFT3D *const sift3d, int r, sift3d_amd_slab_
 }
 
 static int detect_single(SIFT3D *const sift3d, const float *host_dense, const float *d_vol, int nx, int ny, int nz,
-                         double ux, double uy, double uz, Keypoint_store *const kp);
+                         double ux, double uy, double uz, Keypoint_store *const kp, const s3d_typed_src *ts);
 
 int SIFT3D_detect_keypoints(SIFT3D *const sift3d, const Image *const im, Keypoint_store *const kp) /* sift.c:1609 */
 {
@@ -987,7 +1050,7 @@ int SIFT3D_detect_keypoints(SIFT3D *const sift3d, const Image *const im, Keypoin
         }
         return SIFT3D_SUCCESS;
     }
-    rc = detect_single(sift3d, src, NULL, im->nx, im->ny, im->nz, im->ux, im->uy, im->uz, kp);
+    rc = detect_single(sift3d, src, NULL, im->nx, im->ny, im->nz, im->ux, im->uy, im->uz, kp, NULL);
     free(dense);
     return rc;
 }
@@ -997,7 +1060,7 @@ int SIFT3D_detect_keypoints(SIFT3D *const sift3d, const Image *const im, Keypoin
  * count, no extra synchronisation -- whether every voxel was finite; if not, the pass is repeated on the literal kernels
  * (c->verbatim), which reproduce what the reference does with NaNs and infinities (s3d_k_seqmax, s3d_gauss.hip g_verbatim). */
 static int detect_single(SIFT3D *const sift3d, const float *host_dense, const float *d_vol, int nx, int ny, int nz,
-                         double ux, double uy, double uz, Keypoint_store *const kp)
+                         double ux, double uy, double uz, Keypoint_store *const kp, const s3d_typed_src *ts)
 {
     int rc = SIFT3D_FAILURE;
     for (int verbatim = 0; verbatim < 2; verbatim++) {
@@ -1006,7 +1069,7 @@ static int detect_single(SIFT3D *const sift3d, const float *host_dense, const fl
             API_FAIL("sift3d_amd: out of device contexts");
         c = sift_ctx(sift3d);
         c->verbatim = verbatim;
-        rc = set_im_device(sift3d, host_dense, d_vol, nx, ny, nz, ux, uy, uz);
+        rc = set_im_device(sift3d, host_dense, d_vol, nx, ny, nz, ux, uy, uz, ts);
         if (rc == SIFT3D_SUCCESS) rc = build_gpyr_dev(sift3d, c, 1);
         if (rc == SIFT3D_SUCCESS) rc = detect_dev(sift3d, c, kp);
         c->verbatim = 0;
@@ -1037,7 +1100,56 @@ int sift3d_amd_detect_keypoints_dev(SIFT3D *const sift3d, const float *d_vol, in
                                     double uy, double uz, Keypoint_store *const kp)
 {
     if (d_vol == NULL || nx < 1 || ny < 1 || nz < 1) API_FAIL("sift3d_amd_detect_keypoints_dev: bad arguments");
-    return detect_single(sift3d, NULL, d_vol, nx, ny, nz, ux, uy, uz, kp);
+    return detect_single(sift3d, NULL, d_vol, nx, ny, nz, ux, uy, uz, kp, NULL);
+}
+
+/* SIFT3D_detect_keypoints on a volume of 8- or 16-bit integers as stored (include/sift3d_amd.h) */
+int sift3d_amd_detect_keypoints_typed(SIFT3D *const sift3d, const void *vol, int dtype, int on_device, int nx, int ny, int nz,
+                                      double ux, double uy, double uz, double slope, double inter, Keypoint_store *const kp)
+{
+    const int es = s3d_k_typed_elem_size(dtype);
+    if (sift3d == NULL || vol == NULL || kp == NULL) API_FAIL("sift3d_amd_detect_keypoints_typed: null argument");
+    if (nx < 1 || ny < 1 || nz < 1) API_FAIL("sift3d_amd_detect_keypoints_typed: bad dimensions %d x %d x %d", nx, ny, nz);
+    if (es == 0 && dtype != SIFT3D_AMD_F32)
+        API_FAIL("sift3d_amd_detect_keypoints_typed: element type %d is not uint8, int8, uint16, int16 or float32", dtype);
+    if (!isfinite(slope) || !isfinite(inter)) API_FAIL("sift3d_amd_detect_keypoints_typed: slope and inter must be finite");
+    if (slope == 0.0) slope = 1.0;                         /* read_nii's rule (nifti.c:96-98) */
+    if (dtype == SIFT3D_AMD_F32 || (!on_device && mgpu_for(sift3d) > 1)) {
+        /* a float volume, or several GPUs (the Z-slab transport is float: converted here, correct, without the saving) */
+        Image im;
+        float *conv = NULL;
+        int rc;
+        if (dtype == SIFT3D_AMD_F32) {
+            if (slope != 1.0 || inter != 0.0)
+                API_FAIL("sift3d_amd_detect_keypoints_typed: a float32 volume takes slope 1 and inter 0");
+            if (on_device) return sift3d_amd_detect_keypoints_dev(sift3d, (const float *)vol, nx, ny, nz, ux, uy, uz, kp);
+        } else {
+            const size_t n = (size_t)nx * ny * nz;
+            if ((conv = (float *)malloc(n * sizeof(float))) == NULL) API_FAIL("sift3d_amd_detect_keypoints_typed: out of memory");
+            for (size_t i = 0; i < n; i++) {
+                const double raw = dtype == SIFT3D_AMD_U8 ? (double)((const uint8_t *)vol)[i] :
+                                   dtype == SIFT3D_AMD_I8 ? (double)((const int8_t *)vol)[i] :
+                                   dtype == SIFT3D_AMD_U16 ? (double)((const uint16_t *)vol)[i] : (double)((const int16_t *)vol)[i];
+                conv[i] = (float)(raw * slope + inter);
+            }
+        }
+        init_im(&im);
+        im.nx = nx; im.ny = ny; im.nz = nz; im.nc = 1;
+        im.ux = ux; im.uy = uy; im.uz = uz;
+        im_default_stride(&im);
+        im.data = conv ? conv : (float *)(uintptr_t)vol;   /* (read only) */
+        rc = SIFT3D_detect_keypoints(sift3d, &im, kp);
+        free(conv);
+        return rc;
+    }
+    if (mgpu_for(sift3d) > 1)
+        API_FAIL("sift3d_amd_detect_keypoints_typed: a device volume with several GPUs is not supported (pass the host volume)");
+    if (on_device && ((uintptr_t)vol & (uintptr_t)(es - 1)))
+        API_FAIL("sift3d_amd_detect_keypoints_typed: the device volume is not aligned to its element size");
+    {
+        const s3d_typed_src ts = {vol, dtype, on_device != 0, slope, inter};
+        return detect_single(sift3d, NULL, NULL, nx, ny, nz, ux, uy, uz, kp, &ts);
+    }
 }
 
 /* Host-only planning: size the pyramids and build the filter bank for an nx x ny x nz volume exactly as

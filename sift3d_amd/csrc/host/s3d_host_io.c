@@ -246,84 +246,170 @@ static int s3d_gz_read_all(gzFile gz, void *dst, size_t bytes)
     return 0;
 }
 
-int read_nii(const char *path, Image *const im)
-{
+/* A NIfTI-1 file between its header and its voxels: what read_nii and sift3d_amd_read_nii_native share.  s3d_nii_open reads
+ * and checks the header (byte order, dimensionality, datatype, units, scaling), s3d_nii_read_voxels the voxels as the file
+ * stores them (byte-swapped where the file is) into f->raw, s3d_nii_close releases everything. */
+typedef struct {
+    const char *path;
+    char *hdr_path;
+    gzFile gz;
     s3d_nifti1_header h;
-    gzFile gz = NULL;
-    void *raw = NULL;
-    int rc = SIFT3D_FAILURE;
-    char *hdr_path = s3d_hdr_name_for_img(path);          /* Analyze / NIfTI pair: header lives beside */
+    int swapped, single;
+    int nx, ny, nz, nc;
+    double u[3], slope, inter;
+    size_t tsize;
+    void *raw;
+} s3d_nii_file;
+
+static void s3d_nii_close(s3d_nii_file *f)
+{
+    if (f->gz) gzclose(f->gz);
+    free(f->raw);
+    free(f->hdr_path);
+    f->gz = NULL; f->raw = NULL; f->hdr_path = NULL;
+}
+
+static int s3d_nii_open(const char *path, s3d_nii_file *f)
+{
+    s3d_nifti1_header *const h = &f->h;
+    memset(f, 0, sizeof(*f));
+    f->path = path;
+    f->hdr_path = s3d_hdr_name_for_img(path);             /* Analyze / NIfTI pair: header lives beside */
 
     /* gzopen/gzread pass uncompressed files through unchanged, so one code path serves .nii and .nii.gz */
-    if ((gz = gzopen(hdr_path ? hdr_path : path, "rb")) == NULL || s3d_gz_read_all(gz, &h, sizeof(h))) {
+    if ((f->gz = gzopen(f->hdr_path ? f->hdr_path : path, "rb")) == NULL || s3d_gz_read_all(f->gz, h, sizeof(*h))) {
         S3D_MSG("read_nii: failure loading file %s", path);
-        goto done;
+        return SIFT3D_FAILURE;
     }
-    int swapped = 0;
-    if (h.sizeof_hdr != 348) {
-        s3d_nii_swap_header(&h);
-        swapped = 1;
-        if (h.sizeof_hdr != 348) { S3D_MSG("read_nii: failure loading file %s", path); goto done; }
+    if (h->sizeof_hdr != 348) {
+        s3d_nii_swap_header(h);
+        f->swapped = 1;
+        if (h->sizeof_hdr != 348) { S3D_MSG("read_nii: failure loading file %s", path); return SIFT3D_FAILURE; }
     }
-    const int single = memcmp(h.magic, "n+1", 4) == 0;
-    if (!single && hdr_path == NULL) {                     /* "ni1" or Analyze header handed in directly */
+    f->single = memcmp(h->magic, "n+1", 4) == 0;
+    if (!f->single && f->hdr_path == NULL) {               /* "ni1" or Analyze header handed in directly */
         S3D_MSG("read_nii: failure loading file %s", path);
-        goto done;
+        return SIFT3D_FAILURE;
     }
-    int ndim = h.dim[0];
-    if (ndim < 1 || ndim > 7) { S3D_MSG("read_nii: failure loading file %s", path); goto done; }
+    int ndim = h->dim[0];
+    if (ndim < 1 || ndim > 7) { S3D_MSG("read_nii: failure loading file %s", path); return SIFT3D_FAILURE; }
     int dim[8] = {0, 1, 1, 1, 1, 1, 1, 1};
-    for (int i = 1; i <= ndim; i++) dim[i] = h.dim[i] > 0 ? h.dim[i] : 1;
+    for (int i = 1; i <= ndim; i++) dim[i] = h->dim[i] > 0 ? h->dim[i] : 1;
     /* dimensionality = last dimension greater than 1; 4-D means channels (nifti.c:68-83) */
     int used = ndim;
     while (used > 0 && dim[used] <= 1) used--;
     if (used > 4) {
         S3D_MSG("read_nii: file %s has unsupported dimensionality %d\n", path, used);
-        goto done;
+        return SIFT3D_FAILURE;
     }
-    const size_t tsize = s3d_nii_type_size(h.datatype);
-    if (tsize == 0) {
-        S3D_MSG("read_nii: unsupported datatype %d \n", (int)h.datatype);
-        goto done;
+    f->tsize = s3d_nii_type_size(h->datatype);
+    if (f->tsize == 0) {
+        S3D_MSG("read_nii: unsupported datatype %d \n", (int)h->datatype);
+        return SIFT3D_FAILURE;
     }
     /* voxel sizes; zero / non-finite spacing counts as 1 (what nifticlib hands the reference) */
-    double u[3];
     for (int i = 0; i < 3; i++) {
-        const float p = h.pixdim[i + 1];
-        u[i] = (p != 0.0f && isfinite(p)) ? (double)p : 1.0;
+        const float p = h->pixdim[i + 1];
+        f->u[i] = (p != 0.0f && isfinite(p)) ? (double)p : 1.0;
     }
-    im->ux = u[0]; im->uy = u[1]; im->uz = u[2];
-    im->nx = dim[1]; im->ny = dim[2]; im->nz = dim[3];
-    im->nc = used == 4 ? dim[4] : 1;
-    im_default_stride(im);
-    if (im_resize(im)) goto done;
+    f->nx = dim[1]; f->ny = dim[2]; f->nz = dim[3];
+    f->nc = used == 4 ? dim[4] : 1;
+    f->slope = (double)h->scl_slope;
+    if (f->slope == 0.0) f->slope = 1.0;                  /* ill-formatted image: ignore (nifti.c:96-98) */
+    f->inter = (double)h->scl_inter;
+    return SIFT3D_SUCCESS;
+}
 
-    const size_t count = (size_t)im->nx * im->ny * im->nz * im->nc, bytes = count * tsize;
-    if ((raw = malloc(bytes ? bytes : 1)) == NULL) goto done;
-    if (single) {
-        size_t off = h.vox_offset >= 352.0f ? (size_t)h.vox_offset : 352;
+static int s3d_nii_read_voxels(s3d_nii_file *f)
+{
+    const s3d_nifti1_header *const h = &f->h;
+    const char *const path = f->path;
+    const size_t count = (size_t)f->nx * f->ny * f->nz * f->nc, bytes = count * f->tsize;
+    if ((f->raw = malloc(bytes ? bytes : 1)) == NULL) return SIFT3D_FAILURE;
+    if (f->single) {
+        size_t off = h->vox_offset >= 352.0f ? (size_t)h->vox_offset : 352;
         unsigned char skip[256];
-        for (off -= sizeof(h); off; ) {
+        for (off -= sizeof(*h); off; ) {
             const unsigned n = off > sizeof(skip) ? (unsigned)sizeof(skip) : (unsigned)off;
-            if (gzread(gz, skip, n) != (int)n) { S3D_MSG("read_nii: failure loading file %s", path); goto done; }
+            if (gzread(f->gz, skip, n) != (int)n) { S3D_MSG("read_nii: failure loading file %s", path); return SIFT3D_FAILURE; }
             off -= n;
         }
     } else {
-        gzclose(gz);
-        if ((gz = gzopen(path, "rb")) == NULL) { S3D_MSG("read_nii: failure loading file %s", path); goto done; }
-        if (h.vox_offset > 0.0f && gzseek(gz, (z_off_t)h.vox_offset, SEEK_SET) < 0) goto done;
+        gzclose(f->gz);
+        if ((f->gz = gzopen(path, "rb")) == NULL) { S3D_MSG("read_nii: failure loading file %s", path); return SIFT3D_FAILURE; }
+        if (h->vox_offset > 0.0f && gzseek(f->gz, (z_off_t)h->vox_offset, SEEK_SET) < 0) return SIFT3D_FAILURE;
     }
-    if (s3d_gz_read_all(gz, raw, bytes)) { S3D_MSG("read_nii: failure loading file %s", path); goto done; }
-    if (swapped && tsize > 1) s3d_swap(raw, tsize, count);
+    if (s3d_gz_read_all(f->gz, f->raw, bytes)) { S3D_MSG("read_nii: failure loading file %s", path); return SIFT3D_FAILURE; }
+    if (f->swapped && f->tsize > 1) s3d_swap(f->raw, f->tsize, count);
+    return SIFT3D_SUCCESS;
+}
 
-    double slope = (double)h.scl_slope;
-    if (slope == 0.0) slope = 1.0;                        /* ill-formatted image: ignore (nifti.c:96-98) */
-    s3d_nii_to_image(raw, h.datatype, slope, (double)h.scl_inter, im);
+int read_nii(const char *path, Image *const im)
+{
+    s3d_nii_file f;
+    int rc = SIFT3D_FAILURE;
+    if (s3d_nii_open(path, &f)) goto done;
+    im->ux = f.u[0]; im->uy = f.u[1]; im->uz = f.u[2];
+    im->nx = f.nx; im->ny = f.ny; im->nz = f.nz;
+    im->nc = f.nc;
+    im_default_stride(im);
+    if (im_resize(im)) goto done;
+    if (s3d_nii_read_voxels(&f)) goto done;
+    s3d_nii_to_image(f.raw, f.h.datatype, f.slope, f.inter, im);
     rc = SIFT3D_SUCCESS;
 done:
-    if (gz) gzclose(gz);
-    free(raw);
-    free(hdr_path);
+    s3d_nii_close(&f);
+    return rc;
+}
+
+/* The volume with its elements as stored (include/sift3d_amd.h): the four 8- and 16-bit integer types keep their elements
+ * and hand the header's scaling to the caller; everything else is converted as read_nii converts it. */
+void sift3d_amd_free_volume(sift3d_amd_volume *v)
+{
+    if (v == NULL) return;
+    free(v->data);
+    memset(v, 0, sizeof(*v));
+}
+
+int sift3d_amd_read_nii_native(const char *path, sift3d_amd_volume *out)
+{
+    s3d_nii_file f;
+    int rc = SIFT3D_FAILURE;
+    if (path == NULL || out == NULL) return SIFT3D_FAILURE;
+    memset(out, 0, sizeof(*out));
+    if (s3d_nii_open(path, &f)) goto done;
+    if (f.nc != 1) {
+        S3D_MSG("sift3d_amd_read_nii_native: invalid number of image channels: %d -- only single-channel images "
+                "are supported \n", f.nc);
+        goto done;
+    }
+    if (s3d_nii_read_voxels(&f)) goto done;
+    out->nx = f.nx; out->ny = f.ny; out->nz = f.nz;
+    out->ux = f.u[0]; out->uy = f.u[1]; out->uz = f.u[2];
+    switch (f.h.datatype) {
+    case NII_UINT8: case NII_INT8: case NII_UINT16: case NII_INT16:
+        out->data = f.raw;                                /* ours now */
+        f.raw = NULL;
+        out->dtype = f.h.datatype;
+        out->slope = f.slope; out->inter = f.inter;
+        break;
+    default: {
+        Image im;
+        init_im(&im);
+        im.nx = f.nx; im.ny = f.ny; im.nz = f.nz; im.nc = 1;
+        im_default_stride(&im);
+        if ((im.data = (float *)malloc(sizeof(float) * ((size_t)f.nx * f.ny * f.nz + 1))) == NULL) goto done;
+        s3d_nii_to_image(f.raw, f.h.datatype, f.slope, f.inter, &im);
+        out->data = im.data;
+        out->dtype = SIFT3D_AMD_F32;
+        out->slope = 1.0; out->inter = 0.0;
+        break;
+    }
+    }
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_nii_close(&f);
+    if (rc != SIFT3D_SUCCESS) memset(out, 0, sizeof(*out));
     return rc;
 }
 

@@ -88,6 +88,33 @@ typedef float s3d_f2 __attribute__((ext_vector_type(2)));
 typedef float s3d_f2 __attribute__((vector_size(8)));
 #endif
 
+/* ---- volumes of 8- and 16-bit integers, read as stored (S3D_DT_*) ------------------------------------------------------
+ * A voxel's value is (float)((double)raw * slope + inter) everywhere: two separately rounded f64 operations and one
+ * conversion (every translation unit is compiled with -ffp-contract=off), the expression the NIfTI reader evaluates on the
+ * host (s3d_host_io.c).  Four consecutive elements are ONE load -- a dword of 8-bit, a dwordx2 of 16-bit elements -- taken
+ * apart with shifts; the word types may alias anything, like the character types. */
+typedef uint32_t __attribute__((may_alias)) s3d_u32a;
+typedef uint64_t __attribute__((may_alias)) s3d_u64a;
+struct S3dCvt { double slope, inter; };
+template <class T> __device__ __forceinline__ float s3d_cvt(T raw, const S3dCvt &c)
+{
+    return (float)((double)raw * c.slope + c.inter);
+}
+template <class T, int BYTES = sizeof(T)> struct S3dQuad;
+template <class T> struct S3dQuad<T, 1> {
+    typedef s3d_u32a word;
+    static __device__ __forceinline__ T elem(uint32_t w, int i) { return (T)(uint8_t)(w >> (8 * i)); }
+};
+template <class T> struct S3dQuad<T, 2> {
+    typedef s3d_u64a word;
+    static __device__ __forceinline__ T elem(uint64_t w, int i) { return (T)(uint16_t)(w >> (16 * i)); }
+};
+/* the quad at p (aligned to four elements) */
+template <class T> __device__ __forceinline__ typename S3dQuad<T>::word s3d_ld_quad_raw(const T *p)
+{
+    return *reinterpret_cast<const typename S3dQuad<T>::word *>(p);
+}
+
 /* dynamically sized LDS of a kernel (the size is the launch's third parameter) */
 #ifndef S3D_DYN_LDS
 #define S3D_DYN_LDS(T, name) extern __shared__ __attribute__((aligned(16))) T name[]

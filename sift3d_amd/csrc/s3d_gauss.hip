@@ -761,10 +761,49 @@ k_conv_x_mc(const float *__restrict__ src, float *__restrict__ dst, int nx, int 
  * slack) -- so the body slots of that quad hold the wrong columns, and up to two more edge lanes put the right ones
  * there (columns xp .. nx-2; nx-1 and beyond are the high-edge blends that overwrite those slots anyway) -- and stores
  * only its nx % 4 real outputs. */
-template <int HW, bool DIV, bool RAGGED = false>
-__device__ __forceinline__ void gauss_xy_body(const float *__restrict__ src, float *__restrict__ dst, int nx, int ny, int chunk,
-                                              const S3dTaps &taps, const EdgeFrac &efx, const EdgeFrac &efy, const float div)
+/* SRC: where a row's values come from.  SrcF32 (the default) is a float volume.  SrcInt<T> is a volume of 8- or 16-bit
+ * integers read as stored (s3d_common.h): a lane's quad is one dword / dwordx2 and its two edge values one element each,
+ * they stay RAW while they are in flight (2-4 registers per row instead of 6) and are converted -- and divided, as DIV says
+ * -- when the row is staged.  Only load_row and the head of xpass know the difference; LDS line, ring and Y filter do not.
+ * Rows of such a volume must be whole aligned quads (nx % 4 == 0, base aligned to four elements; not RAGGED). */
+struct XyRawF32 { float4 b; float a0, a1; };
+struct SrcF32 {
+    typedef float elem;
+    typedef XyRawF32 Raw;
+    static constexpr bool typed = false;
+};
+template <class T> struct SrcInt {
+    typedef T elem;
+    struct Raw { typename S3dQuad<T>::word b; T a0, a1; };
+    static constexpr bool typed = true;
+    S3dCvt c;
+};
+/* a row's values as it is staged: a float row is what was loaded (DIV applied there) ... */
+template <bool DIV>
+__device__ __forceinline__ const XyRawF32 &xy_cook(const SrcF32 &, const XyRawF32 &q, float) { return q; }
+/* ... an integer row's are (float)((double)raw * slope + inter), then im_scale's division */
+template <bool DIV, class T>
+__device__ __forceinline__ XyRawF32 xy_cook(const SrcInt<T> &cv, const typename SrcInt<T>::Raw &q, float div)
 {
+    typedef S3dQuad<T> Q;
+    XyRawF32 r;
+    r.b = make_float4(s3d_cvt(Q::elem(q.b, 0), cv.c), s3d_cvt(Q::elem(q.b, 1), cv.c), s3d_cvt(Q::elem(q.b, 2), cv.c),
+                      s3d_cvt(Q::elem(q.b, 3), cv.c));
+    r.a0 = s3d_cvt(q.a0, cv.c);
+    r.a1 = s3d_cvt(q.a1, cv.c);
+    if (DIV) {
+        r.b.x = r.b.x / div; r.b.y = r.b.y / div; r.b.z = r.b.z / div; r.b.w = r.b.w / div;
+        r.a0 = r.a0 / div; r.a1 = r.a1 / div;
+    }
+    return r;
+}
+
+template <int HW, bool DIV, bool RAGGED = false, class SRC = SrcF32>
+__device__ __forceinline__ void gauss_xy_body(const typename SRC::elem *__restrict__ src, float *__restrict__ dst, int nx, int ny, int chunk,
+                                              const S3dTaps &taps, const EdgeFrac &efx, const EdgeFrac &efy, const float div,
+                                              const SRC &cv = SRC())
+{
+    static_assert(!(SRC::typed && RAGGED), "integer sources: whole aligned quads only");
     constexpr int W = 2 * HW + 1;
     constexpr int PAD = (4 - HW % 4) % 4;             /* puts the body at a 16-byte aligned LDS offset */
     constexpr int OFF = PAD + HW;                     /* line[OFF + i] = E_x[x0 + i] ; OFF % 4 == 0 */
@@ -775,7 +814,7 @@ __device__ __forceinline__ void gauss_xy_body(const float *__restrict__ src, flo
     const int x0 = blockIdx.x * XY_STRIP;
     const int xq = x0 + 4 * lane;                     /* this lane's 4 output columns */
     const size_t plane = (size_t)nx * ny;
-    const float *sp = src + (size_t)blockIdx.z * plane;
+    const typename SRC::elem *sp = src + (size_t)blockIdx.z * plane;
     float *dp = dst + (size_t)blockIdx.z * plane;
     const int p0 = blockIdx.y * chunk;
     const int p1 = (p0 + chunk < ny) ? p0 + chunk : ny;
@@ -822,23 +861,29 @@ __device__ __forceinline__ void gauss_xy_body(const float *__restrict__ src, flo
     /* Raw loads of one source row, issued three rows ahead.  They are UNCONDITIONAL on purpose: a load
      * under a divergent `if` makes the compiler wait for it at the join (its destination registers
      * merge with the other path), which turns every prefetch into a synchronous load. */
-    struct Raw { float4 b; float a0, a1; };
+    typedef typename SRC::Raw Raw;
     auto load_row = [&](int y) -> Raw {
         Raw r;
-        const float *row = sp + (size_t)y * nx;
-        if (RAGGED) r.b = ld_quad<true>(row + xq_ld);
-        else r.b = *reinterpret_cast<const float4 *>(row + xq_ld);
-        r.a0 = row[colA];
-        r.a1 = row[colB];
-        if (DIV) {
-            r.b.x = r.b.x / div; r.b.y = r.b.y / div; r.b.z = r.b.z / div; r.b.w = r.b.w / div;
-            r.a0 = r.a0 / div; r.a1 = r.a1 / div;
+        const typename SRC::elem *row = sp + (size_t)y * nx;
+        if constexpr (SRC::typed) {
+            r.b = s3d_ld_quad_raw(row + xq_ld);
+            r.a0 = row[colA];
+            r.a1 = row[colB];
+        } else {
+            if (RAGGED) r.b = ld_quad<true>(row + xq_ld);
+            else r.b = *reinterpret_cast<const float4 *>(row + xq_ld);
+            r.a0 = row[colA];
+            r.a1 = row[colB];
+            if (DIV) {
+                r.b.x = r.b.x / div; r.b.y = r.b.y / div; r.b.z = r.b.z / div; r.b.w = r.b.w / div;
+                r.a0 = r.a0 / div; r.a1 = r.a1 / div;
+            }
         }
         return r;
     };
     /* stage the row in LDS, X-filter this lane's 4 columns */
     int lbuf = 0;
-    auto xpass = [&](const Raw &r) -> float4 {
+    auto xpass = [&](const XyRawF32 &r) -> float4 {
         float *line = line2[lbuf];
         lbuf ^= 1;
         *reinterpret_cast<float4 *>(&line[OFF + 4 * lane]) = r.b;
@@ -902,14 +947,15 @@ __device__ __forceinline__ void gauss_xy_body(const float *__restrict__ src, flo
         for (int d = 0; d + 1 < DEPTH; d++) q[d] = q[d + 1];
         if (t + DEPTH < T) q[DEPTH - 1] = load_row(first_row(c0 + t + DEPTH));
         if (c < 0) c = -c;
+        const XyRawF32 &curf = xy_cook<DIV>(cv, cur, div);   /* (a float row: cur itself) */
         float4 e;
         if (c <= ny - 2) {
-            e = xpass(cur);
+            e = xpass(curf);
         } else {                                          /* high-side virtual row: two X-filtered rows */
             const int j = c - (ny - 1);
             const Raw rb = load_row(ny - 1 - j);
-            const float4 ea = xpass(cur);                 /* row ny-2-j */
-            const float4 eb = xpass(rb);                  /* row ny-1-j */
+            const float4 ea = xpass(curf);                /* row ny-2-j */
+            const float4 eb = xpass(xy_cook<DIV>(cv, rb, div));    /* row ny-1-j */
             e = blend4(ea, eb, efy.f[j]);
         }
         ring[u] = e;
@@ -937,7 +983,7 @@ __device__ __forceinline__ void gauss_xy_body(const float *__restrict__ src, flo
 #pragma unroll
             for (int d = 0; d + 1 < DEPTH; d++) q[d] = q[d + 1];
             q[DEPTH - 1] = load_row(first_row(c0 + t + DEPTH));
-            ring[u] = xpass(cur);
+            ring[u] = xpass(xy_cook<DIV>(cv, cur, div));
             const float4 acc = ring_dot<HW>(ring, u, taps);
             if (RAGGED) { if (live) store_out(dp + (size_t)(p0 + t - 2 * HW) * nx + xq, acc); }
             else if (live) *reinterpret_cast<float4 *>(dp + (size_t)(p0 + t - 2 * HW) * nx + xq) = acc;
@@ -969,6 +1015,27 @@ k_gauss_xy_div(const float *__restrict__ src, float *__restrict__ dst, int nx, i
     const float m = *d_div;
     gauss_xy_body<HW, true, RAGGED>(src, dst, nx, ny, chunk, taps, efx, efy, m == 0.0f ? 1.0f : m);   /* k_scale_div leaves an all-zero image alone */
 }
+
+/* k_gauss_xy_div on a volume of 8- or 16-bit integers (the first filter of a pyramid whose input arrived as stored): the
+ * conversion and the division ride in the loads.  (Its name keeps clear of the two kernel families whose machine code
+ * identifies the measured Gaussian, sift3d_amd/codeobj.py.) */
+template <int HW, class T>
+__global__ void __launch_bounds__(64, GAUSS_XY_WAVES(HW))
+k_first_xy_typed(const T *__restrict__ src, float *__restrict__ dst, int nx, int ny, int chunk, S3dTaps taps,
+                 EdgeFrac efx, EdgeFrac efy, const float *__restrict__ d_div, S3dCvt c)
+{
+    const float m = *d_div;
+    SrcInt<T> cv;
+    cv.c = c;
+    gauss_xy_body<HW, true, false, SrcInt<T>>(src, dst, nx, ny, chunk, taps, efx, efy, m == 0.0f ? 1.0f : m, cv);
+}
+
+/* an integer source of launch_fast: the volume, its element type (S3D_DT_*) and scaling */
+struct TypedSrc { const void *p; int dtype; S3dCvt c; };
+/* The widest half width instantiated for integer sources.  At 9 the march's unrolled steps, a conversion larger each than the
+ * float kernel's, pass the compiler's limit for a full unroll, and a ring that is indexed by a loop counter lives in a private
+ * segment (320 bytes per lane), which no kernel of the step may have: such a filter converts first (s3d_k_convert_f32). */
+#define TYPED_MAX_HW 8
 
 static int fast_eligible(int nx, int ny, int nz, int nc, const float uf[3], int width)
 {
@@ -1041,7 +1108,8 @@ extern "C" void s3d_k_gauss_set_events(void *before_xy, void *between, void *aft
  * Z-slab needs valid source planes [z0-HW, z1+HW) (clamped to the volume), i.e. the neighbours' halos. */
 template <int HW>
 static int launch_fast(const float *d_src, float *d_dst, float *d_tmp, int nx, int ny, int nz, int z0, int z1,
-                       const S3dTaps &t, hipStream_t st, const float *d_div = nullptr, float *d_maxout = nullptr)
+                       const S3dTaps &t, hipStream_t st, const float *d_div = nullptr, float *d_maxout = nullptr,
+                       const TypedSrc *ts = nullptr)
 {
     EdgeFrac ex, ey, ez;
     if (edge_fracs(nx, HW, &ex) || edge_fracs(ny, HW, &ey) || edge_fracs(nz, HW, &ez)) S3D_FAIL("edge table");
@@ -1059,7 +1127,15 @@ static int launch_fast(const float *d_src, float *d_dst, float *d_tmp, int nx, i
     if (g_ev[0]) S3D_HIP(hipEventRecord(g_ev[0], st));
     const bool ragged = nx % 4 != 0;
     const dim3 gxy(s3d_div_up(nx, XY_STRIP), ncy, zb - za);
-    if (d_div && ragged)
+    if (ts) {                                             /* (s3d_k_sep_fir_div_typed: whole volume, aligned quads, d_div) */
+        if (ragged || !d_div || za != 0 || HW > TYPED_MAX_HW) S3D_FAIL("integer source: not eligible");
+        if constexpr (HW <= TYPED_MAX_HW) switch (ts->dtype) {
+#define S3D_XYT(DT, T) case DT: hipLaunchKernelGGL((k_first_xy_typed<HW, T>), gxy, dim3(64), 0, st, (const T *)ts->p, d_tmp, nx, ny, cy, t, ex, ey, d_div, ts->c); break;
+        S3D_XYT(S3D_DT_U8, uint8_t) S3D_XYT(S3D_DT_I8, int8_t) S3D_XYT(S3D_DT_U16, uint16_t) S3D_XYT(S3D_DT_I16, int16_t)
+#undef S3D_XYT
+        default: S3D_FAIL("integer source: element type");
+        }
+    } else if (d_div && ragged)
         hipLaunchKernelGGL((k_gauss_xy_div<HW, true>), gxy, dim3(64), 0, st, d_src + za * plane, d_tmp + za * plane, nx, ny, cy, t, ex, ey, d_div);
     else if (d_div)
         hipLaunchKernelGGL((k_gauss_xy_div<HW>), dim3(s3d_div_up(nx, XY_STRIP), ncy, zb - za), dim3(64), 0, st,
@@ -1137,18 +1213,19 @@ static int fast_xy_eligible(int nx, int ny, int nz, int nc, const float uf[3], i
 }
 
 static int fast_dispatch(const float *d_src, float *d_dst, float *d_tmp, int nx, int ny, int nz, int z0, int z1,
-                         int hw, const S3dTaps &t, hipStream_t st, const float *d_div = nullptr, float *d_maxout = nullptr)
+                         int hw, const S3dTaps &t, hipStream_t st, const float *d_div = nullptr, float *d_maxout = nullptr,
+                         const TypedSrc *ts = nullptr)
 {
     switch (hw) {
-    case 1: return launch_fast<1>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 2: return launch_fast<2>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 3: return launch_fast<3>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 4: return launch_fast<4>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 5: return launch_fast<5>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 6: return launch_fast<6>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 7: return launch_fast<7>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 8: return launch_fast<8>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
-    case 9: return launch_fast<9>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout);
+    case 1: return launch_fast<1>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 2: return launch_fast<2>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 3: return launch_fast<3>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 4: return launch_fast<4>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 5: return launch_fast<5>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 6: return launch_fast<6>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 7: return launch_fast<7>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 8: return launch_fast<8>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
+    case 9: return launch_fast<9>(d_src, d_dst, d_tmp, nx, ny, nz, z0, z1, t, st, d_div, d_maxout, ts);
     default: break;
     }
     S3D_FAIL("half width not instantiated");
@@ -1470,6 +1547,31 @@ extern "C" int s3d_k_sep_fir_div(const float *d_src, float *d_dst, float *d_tmp,
     if (conv_axis_range(d_dst, d_tmp, nx, ny, nz, 1, 1, za, zb, taps, width, uf[1], stream)) return S3D_ERR;
     if (conv_axis_range(d_tmp, d_dst, nx, ny, nz, 1, 2, z0, z1, taps, width, uf[2], stream)) return S3D_ERR;
     return S3D_OK;
+}
+
+/* s3d_k_sep_fir_div over a whole volume of 8- or 16-bit integers: the fused unit-spacing kernels only (the table-driven x
+ * pass and ragged rows read floats: callers convert first) */
+extern "C" int s3d_k_sep_fir_div_typed_eligible(const void *d_src, int dtype, int nx, int ny, int nz, const float uf[3], int width)
+{
+    const int es = s3d_k_typed_elem_size(dtype);
+    if (!(width >= 1 && width <= S3D_MAX_TAPS && (width & 1)) || es == 0 || d_src == nullptr) return 0;
+    if ((nx & 3) || ((uintptr_t)d_src & (uintptr_t)(4 * es - 1)) || width / 2 > TYPED_MAX_HW) return 0;
+    return fast_eligible(nx, ny, nz, 1, uf, width);
+}
+
+extern "C" int s3d_k_sep_fir_div_typed(const void *d_src, int dtype, double slope, double inter, float *d_dst, float *d_tmp, int nx,
+                                       int ny, int nz, const float uf[3], const float *taps, int width, const float *d_div,
+                                       s3d_stream stream)
+{
+    S3dTaps t;
+    if (check_taps(taps, width, &t)) return S3D_ERR;
+    if (nx < 1 || ny < 1 || nz < 1 || d_div == nullptr || d_dst == nullptr || d_tmp == nullptr) S3D_FAIL("bad arguments");
+    if (d_tmp == d_dst) S3D_FAIL("scratch must not alias dst");
+    if (!(slope - slope == 0.0) || !(inter - inter == 0.0)) S3D_FAIL("slope and inter must be finite");
+    if (!s3d_k_sep_fir_div_typed_eligible(d_src, dtype, nx, ny, nz, uf, width))
+        S3D_FAIL("configuration not eligible for the fused convert + scale + filter");
+    const TypedSrc ts = {d_src, dtype, {slope, inter}};
+    return fast_dispatch(nullptr, d_dst, d_tmp, nx, ny, nz, 0, nz, width / 2, t, (hipStream_t)stream, d_div, nullptr, &ts);
 }
 
 extern "C" int s3d_k_sep_fir_path(const float *d_src, float *d_dst, float *d_tmp, int nx, int ny, int nz, int nc,

@@ -494,3 +494,156 @@ extern "C" int s3d_k_decimate2_nc(const float *d_src, int nx, int ny, int nz, in
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }
+
+/* ---- volumes of 8- and 16-bit integers, read as stored (s3d_common.h: S3dCvt, S3dQuad) ----------------------------------------
+ * Both kernels take the volume as: `head` elements in front of the first address aligned to four elements, whole quads (one
+ * dword / dwordx2 load each), and what is left behind them; the few loose elements go to the first threads of block 0. */
+template <class T> struct TypedSpan {
+    const T *p;          /* the volume */
+    size_t n, head, nq;  /* elements; loose ones in front; quads behind them */
+};
+template <class T> static TypedSpan<T> typed_span(const void *d_src, size_t n)
+{
+    TypedSpan<T> s;
+    s.p = (const T *)d_src;
+    s.n = n;
+    const size_t mis = ((uintptr_t)d_src / sizeof(T)) & 3;
+    s.head = mis ? 4 - mis : 0;
+    if (s.head > n) s.head = n;
+    s.nq = (n - s.head) / 4;
+    return s;
+}
+
+/* dst[i] = value of src[i]: four elements per lane and load, one 16-byte store (dword aligned: s3d_f4u), four independent
+ * loads per thread and turn as in k_absmax. */
+template <class T>
+__global__ void __launch_bounds__(RED_BLOCK) k_convert_f32(TypedSpan<T> s, S3dCvt c, float *__restrict__ dst)
+{
+    const T *__restrict__ body = s.p + s.head;
+    float *__restrict__ obody = dst + s.head;
+    const size_t stride = (size_t)gridDim.x * RED_BLOCK;
+    auto put = [&](size_t q, typename S3dQuad<T>::word w) {
+        s3d_f4u o;
+        o.x = s3d_cvt(S3dQuad<T>::elem(w, 0), c); o.y = s3d_cvt(S3dQuad<T>::elem(w, 1), c);
+        o.z = s3d_cvt(S3dQuad<T>::elem(w, 2), c); o.w = s3d_cvt(S3dQuad<T>::elem(w, 3), c);
+        *reinterpret_cast<s3d_f4u *>(obody + 4 * q) = o;
+    };
+    size_t i = (size_t)blockIdx.x * RED_BLOCK + threadIdx.x;
+    for (; i + (ABSMAX_UNROLL - 1) * stride < s.nq; i += ABSMAX_UNROLL * stride) {
+        typename S3dQuad<T>::word w[ABSMAX_UNROLL];
+#pragma unroll
+        for (int k = 0; k < ABSMAX_UNROLL; k++) w[k] = s3d_ld_quad_raw(body + 4 * (i + k * stride));
+#pragma unroll
+        for (int k = 0; k < ABSMAX_UNROLL; k++) put(i + k * stride, w[k]);
+    }
+    for (; i < s.nq; i += stride) put(i, s3d_ld_quad_raw(body + 4 * i));
+    if (blockIdx.x == 0) {
+        const size_t tail0 = s.head + 4 * s.nq, loose = s.head + (s.n - tail0);       /* <= 6 */
+        if (threadIdx.x < loose) {
+            const size_t e = threadIdx.x < s.head ? threadIdx.x : tail0 + (threadIdx.x - s.head);
+            dst[e] = s3d_cvt(s.p[e], c);
+        }
+    }
+}
+
+/* max |value|: the value is monotone in the raw element -- the product with slope, the sum with inter and the conversion to
+ * float are each rounded monotonically, overflow to an infinity included -- so |value| is largest at the smallest or at the
+ * largest raw element: integer minimum and maximum per thread, two conversions, then k_absmax's reduction over the bit
+ * patterns.  (Integers hold no NaN and slope / inter are finite: the result is never one.) */
+template <class T>
+__global__ void __launch_bounds__(RED_BLOCK) k_absmax_typed(TypedSpan<T> s, S3dCvt c, unsigned *out)
+{
+    const T *__restrict__ body = s.p + s.head;
+    const size_t stride = (size_t)gridDim.x * RED_BLOCK;
+    int lo = 0x7fffffff, hi = -0x7fffffff - 1;
+    auto take = [&](int v) { lo = v < lo ? v : lo; hi = v > hi ? v : hi; };
+    auto take4 = [&](typename S3dQuad<T>::word w) {
+        take(S3dQuad<T>::elem(w, 0)); take(S3dQuad<T>::elem(w, 1)); take(S3dQuad<T>::elem(w, 2)); take(S3dQuad<T>::elem(w, 3));
+    };
+    size_t i = (size_t)blockIdx.x * RED_BLOCK + threadIdx.x;
+    for (; i + (ABSMAX_UNROLL - 1) * stride < s.nq; i += ABSMAX_UNROLL * stride) {
+        typename S3dQuad<T>::word w[ABSMAX_UNROLL];
+#pragma unroll
+        for (int k = 0; k < ABSMAX_UNROLL; k++) w[k] = s3d_ld_quad_raw(body + 4 * (i + k * stride));
+#pragma unroll
+        for (int k = 0; k < ABSMAX_UNROLL; k++) take4(w[k]);
+    }
+    for (; i < s.nq; i += stride) take4(s3d_ld_quad_raw(body + 4 * i));
+    if (blockIdx.x == 0) {
+        const size_t tail0 = s.head + 4 * s.nq, loose = s.head + (s.n - tail0);
+        if (threadIdx.x < loose) take(s.p[threadIdx.x < s.head ? threadIdx.x : tail0 + (threadIdx.x - s.head)]);
+    }
+    unsigned m = 0u;
+    if (lo <= hi) m = umax(absbits(s3d_cvt((T)lo, c)), absbits(s3d_cvt((T)hi, c)));    /* (a thread that saw no element: 0) */
+    m = block_max(m);
+    if (threadIdx.x == 0) atomicMax(out, m);
+}
+
+extern "C" int s3d_k_typed_elem_size(int dtype)
+{
+    return dtype == S3D_DT_U8 || dtype == S3D_DT_I8 ? 1 : dtype == S3D_DT_I16 || dtype == S3D_DT_U16 ? 2 : 0;
+}
+
+static int typed_args(const void *d_src, int dtype, double slope, double inter, const char **why)
+{
+    const int es = s3d_k_typed_elem_size(dtype);
+    *why = nullptr;
+    if (es == 0) *why = "element type is not one of uint8, int8, uint16, int16";
+    else if (d_src == nullptr || ((uintptr_t)d_src & (uintptr_t)(es - 1))) *why = "volume is null or not aligned to its element size";
+    else if (!(slope - slope == 0.0) || !(inter - inter == 0.0)) *why = "slope and inter must be finite";
+    return *why ? S3D_ERR : S3D_OK;
+}
+
+template <class T>
+static int launch_convert(const void *d_src, size_t n, S3dCvt c, float *d_dst, hipStream_t st)
+{
+    const TypedSpan<T> s = typed_span<T>(d_src, n);
+    unsigned blocks = s3d_div_up(s.nq + 1, RED_BLOCK * ABSMAX_UNROLL);
+    if (blocks > RED_MAX_BLOCKS) blocks = RED_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_convert_f32<T>, dim3(blocks), dim3(RED_BLOCK), 0, st, s, c, d_dst);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+extern "C" int s3d_k_convert_f32(const void *d_src, int dtype, size_t n, double slope, double inter, float *d_dst, s3d_stream stream)
+{
+    const char *why;
+    const S3dCvt c = {slope, inter};
+    hipStream_t st = (hipStream_t)stream;
+    if (typed_args(d_src, dtype, slope, inter, &why)) S3D_FAIL(why);
+    if (d_dst == nullptr || ((uintptr_t)d_dst & 3)) S3D_FAIL("destination is null or not dword aligned");
+    if (n == 0) return S3D_OK;
+    switch (dtype) {
+    case S3D_DT_U8: return launch_convert<uint8_t>(d_src, n, c, d_dst, st);
+    case S3D_DT_I8: return launch_convert<int8_t>(d_src, n, c, d_dst, st);
+    case S3D_DT_U16: return launch_convert<uint16_t>(d_src, n, c, d_dst, st);
+    default: return launch_convert<int16_t>(d_src, n, c, d_dst, st);
+    }
+}
+
+template <class T>
+static int launch_absmax_typed(const void *d_src, size_t n, S3dCvt c, float *d_max, hipStream_t st)
+{
+    const TypedSpan<T> s = typed_span<T>(d_src, n);
+    unsigned blocks = s3d_div_up(s.nq + 1, RED_BLOCK * ABSMAX_UNROLL);
+    if (blocks > ABSMAX_MAX_BLOCKS) blocks = ABSMAX_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_absmax_typed<T>, dim3(blocks), dim3(RED_BLOCK), 0, st, s, c, (unsigned *)d_max);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+extern "C" int s3d_k_absmax_typed(const void *d_src, int dtype, size_t n, double slope, double inter, float *d_max, s3d_stream stream)
+{
+    const char *why;
+    const S3dCvt c = {slope, inter};
+    hipStream_t st = (hipStream_t)stream;
+    if (typed_args(d_src, dtype, slope, inter, &why)) S3D_FAIL(why);
+    S3D_HIP(hipMemsetAsync(d_max, 0, sizeof(float), st));
+    if (n == 0) return S3D_OK;
+    switch (dtype) {
+    case S3D_DT_U8: return launch_absmax_typed<uint8_t>(d_src, n, c, d_max, st);
+    case S3D_DT_I8: return launch_absmax_typed<int8_t>(d_src, n, c, d_max, st);
+    case S3D_DT_U16: return launch_absmax_typed<uint16_t>(d_src, n, c, d_max, st);
+    default: return launch_absmax_typed<int16_t>(d_src, n, c, d_max, st);
+    }
+}

@@ -29,6 +29,12 @@ def bind_extensions(L: C.CDLL) -> None:
     L.sift3d_amd_nn_match_dev.argtypes = [_vp, C.c_size_t, C.c_long, _vp, C.c_size_t, C.c_long, C.c_float,
                                           P(C.c_int), _vp]
     L.sift3d_amd_last_error.restype = C.c_char_p
+    L.sift3d_amd_detect_keypoints_typed.argtypes = [P(abi.SIFT3D), _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                    C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                    P(abi.Keypoint_store)]
+    L.sift3d_amd_read_nii_native.argtypes = [C.c_char_p, P(abi.Volume)]
+    L.sift3d_amd_free_volume.argtypes = [P(abi.Volume)]
+    L.sift3d_amd_free_volume.restype = None
 
 
 class DeviceLib:
@@ -61,6 +67,13 @@ class DeviceLib:
         L.s3d_k_gauss_set_events.argtypes = [_vp, _vp, _vp]
         L.s3d_k_gauss_set_events.restype = None
         L.s3d_k_dogmax.argtypes = [_vp, _vp, C.c_size_t, _vp, _vp]
+        # volumes of 8- / 16-bit integers as stored: (src, dtype code, ...)
+        L.s3d_k_typed_elem_size.argtypes = [C.c_int]
+        L.s3d_k_convert_f32.argtypes = [_vp, C.c_int, C.c_size_t, C.c_double, C.c_double, _vp, _vp]
+        L.s3d_k_absmax_typed.argtypes = [_vp, C.c_int, C.c_size_t, C.c_double, C.c_double, _vp, _vp]
+        L.s3d_k_sep_fir_div_typed_eligible.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
+        L.s3d_k_sep_fir_div_typed.argtypes = [_vp, C.c_int, C.c_double, C.c_double, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                              _f32p, _f32p, C.c_int, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -129,6 +142,17 @@ class DeviceLib:
                                             m.ctypes.data_as(C.POINTER(C.c_int)), stream)
         self.check(rc, "sift3d_amd_nn_match_dev")
         return m
+
+    # --- volumes of 8- / 16-bit integers as stored ----------------------------------------------------
+    def convert_f32(self, d_src: int, dtype, n: int, slope: float, inter: float, d_dst: int, stream=None) -> None:
+        """d_dst[i] = (float)((double)d_src[i] * slope + inter); dtype: a numpy dtype of the four integer types."""
+        self.check(self.L.s3d_k_convert_f32(_vp(d_src), abi.TYPED_DTYPES[np.dtype(dtype)], n, slope, inter, _vp(d_dst),
+                                            _vp(stream)), "s3d_k_convert_f32")
+
+    def absmax_typed(self, d_src: int, dtype, n: int, slope: float, inter: float, d_max: int, stream=None) -> None:
+        """*d_max = max |converted d_src[i]| (s3d_k_absmax_typed)."""
+        self.check(self.L.s3d_k_absmax_typed(_vp(d_src), abi.TYPED_DTYPES[np.dtype(dtype)], n, slope, inter, _vp(d_max),
+                                             _vp(stream)), "s3d_k_absmax_typed")
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
