@@ -1,12 +1,15 @@
 /* kpSift3D -- keypoints and descriptors of one volume, on the MI355X.
  *
  * Same command line, outputs and messages as the reference program (cli/kpSift3D.c:1-228):
- *     kpSift3D [SIFT3D options] [--keys keys.csv] [--desc desc.csv] [--draw points.nii] image.nii
+ *     kpSift3D [SIFT3D options] [--keys keys.csv] [--desc desc.csv] [--draw points.nii] [--mask mask.nii] image.nii
  * linked against libsift3d_amd.so instead of libsift3D/libimutil.  Every call below is the reference's
- * API; detection and description run as HIP kernels, the rest is host C.
+ * API; detection and description run as HIP kernels, the rest is host C.  --mask is this program's own: keypoints inside a
+ * region of interest only (sift3d_amd_set_mask).
  */
 #include <getopt.h>
+#include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "sift3d_amd.h"
 
@@ -29,6 +32,8 @@ static const char usage[] =
     "       Draws the keypoints in image space. \n"
     "       Supported file formats: .dcm, .nii, .nii.gz, directory \n"
     "At least one of the output options must be specified. \n"
+    " --mask [filename] \n"
+    "       Keeps the keypoints on non-zero voxels of this image (same dimensions) only. \n"
     "\n";
 
 static void complain(const char *msg)
@@ -49,18 +54,64 @@ static void complain_path(const char *what, const char *path)
     complain(msg);
 }
 
+/* The mask file as one byte per voxel, non-zero -> 1 (a uint8 file is taken as it is stored: any non-zero byte counts);
+ * the scaling of the header does not apply to a mask: the stored elements are tested.  NULL: failure, message printed. */
+static unsigned char *read_mask(const char *path, int nx, int ny, int nz)
+{
+    sift3d_amd_volume v;
+    unsigned char *m;
+    size_t n;
+    if (sift3d_amd_read_nii_native(path, &v)) {
+        complain("Could not read the mask.");
+        return NULL;
+    }
+    if (v.nx != nx || v.ny != ny || v.nz != nz) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "The mask is %d x %d x %d but the image is %d x %d x %d.", v.nx, v.ny, v.nz, nx, ny, nz);
+        complain(msg);
+        sift3d_amd_free_volume(&v);
+        return NULL;
+    }
+    n = (size_t)nx * ny * nz;
+    if ((m = (unsigned char *)malloc(n)) == NULL) {
+        complain("Out of memory.");
+        sift3d_amd_free_volume(&v);
+        return NULL;
+    }
+    switch (v.dtype) {
+    case SIFT3D_AMD_U8:
+    case SIFT3D_AMD_I8:
+        for (size_t i = 0; i < n; i++) m[i] = ((const uint8_t *)v.data)[i] != 0;
+        break;
+    case SIFT3D_AMD_U16:
+    case SIFT3D_AMD_I16:
+        for (size_t i = 0; i < n; i++) m[i] = ((const uint16_t *)v.data)[i] != 0;
+        break;
+    case SIFT3D_AMD_F32:
+        for (size_t i = 0; i < n; i++) m[i] = ((const float *)v.data)[i] != 0.0f;
+        break;
+    default:
+        complain("Unsupported element type in the mask.");
+        free(m);
+        m = NULL;
+    }
+    sift3d_amd_free_volume(&v);
+    return m;
+}
+
 int main(int argc, char *argv[])
 {
-    enum { OPT_KEYS = 'a', OPT_DESC, OPT_DRAW };
+    enum { OPT_KEYS = 'a', OPT_DESC, OPT_DRAW, OPT_MASK };
     static const struct option outputs[] = {{"keys", required_argument, NULL, OPT_KEYS},
                                             {"desc", required_argument, NULL, OPT_DESC},
                                             {"draw", required_argument, NULL, OPT_DRAW},
+                                            {"mask", required_argument, NULL, OPT_MASK},
                                             {0, 0, 0, 0}};
     SIFT3D sift3d;
     Image im;
     Keypoint_store kp;
     SIFT3D_Descriptor_store desc;
-    const char *keys_path = NULL, *desc_path = NULL, *draw_path = NULL;
+    const char *keys_path = NULL, *desc_path = NULL, *draw_path = NULL, *mask_path = NULL;
 
     switch (parse_gnu(argc, argv)) {
     case SIFT3D_HELP:
@@ -83,6 +134,7 @@ int main(int argc, char *argv[])
         if (c == OPT_KEYS) keys_path = optarg;
         else if (c == OPT_DESC) desc_path = optarg;
         else if (c == OPT_DRAW) draw_path = optarg;
+        else if (c == OPT_MASK) mask_path = optarg;
         else return 1;
     }
     if (!keys_path && !desc_path && !draw_path) {
@@ -105,6 +157,16 @@ int main(int argc, char *argv[])
     if (im_read(im_path, &im)) {
         complain("Could not read image.");
         return 1;
+    }
+    if (mask_path) {
+        unsigned char *const mask = read_mask(mask_path, im.nx, im.ny, im.nz);
+        if (mask == NULL) return 1;
+        if (sift3d_amd_set_mask(&sift3d, mask, 0, im.nx, im.ny, im.nz)) {
+            free(mask);
+            complain_bug("Failed to set the mask.");
+            return 1;
+        }
+        free(mask);
     }
     if (SIFT3D_detect_keypoints(&sift3d, &im, &kp)) {
         complain_bug("Failed to detect keypoints.");

@@ -225,6 +225,20 @@ int s3d_k_compact_bits_multi(const unsigned long long *d_bits, size_t nwords, in
                              uint32_t *d_idx, uint32_t *d_tag, uint32_t tag, uint32_t capacity, uint32_t *d_count,
                              uint32_t *d_scratch, s3d_stream stream);
 
+/* s3d_k_compact_bits_multi over d_bits[w] & d_and[w]: d_and holds nwords words shared by all nseg segments (the octave's
+ * region-of-interest bitmap, s3d_k_mask_pack); d_and == NULL is s3d_k_compact_bits_multi.  The count advances by the
+ * population of the ANDed words. */
+int s3d_k_compact_bits_multi_and(const unsigned long long *d_bits, size_t nwords, int nseg, size_t seg_stride, uint32_t idx_base,
+                                 uint32_t *d_idx, uint32_t *d_tag, uint32_t tag, uint32_t capacity, uint32_t *d_count,
+                                 uint32_t *d_scratch, const unsigned long long *d_and, s3d_stream stream);
+/* A byte mask of the input volume (rows of nx bytes, planes of nx * ny) as one bit per voxel of the octave it was decimated
+ * to `shift` times (dims onx x ony x onz, from the pyramid): bit i = x + onx * (y + ony * z) of d_bits is set iff the byte at
+ * (x << shift, y << shift, z << shift) is non-zero -- the voxel of the input that octave voxel is (im_downsample_2x takes
+ * voxel (2x, 2y, 2z), imutil.c:1742-1768).  Writes ceil(onx * ony * onz / 64) words, every one of them, once; bits past the
+ * last voxel are zero. */
+int s3d_k_mask_pack(const unsigned char *d_mask, int nx, int ny, int onx, int ony, int onz, int shift,
+                    unsigned long long *d_bits, s3d_stream stream);
+
 /* ---- keypoints ----------------------------------------------------------------------------------- */
 typedef struct {
     const float *d_level[S3D_MAX_OCTAVES * S3D_MAX_LEVELS]; /* GSS level data, [o*num_levels + (s-first_level)] */

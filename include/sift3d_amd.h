@@ -436,7 +436,8 @@ int sift3d_amd_nn_match_dev(const float *d_a, size_t a_stride, long na, const fl
 /* Diagnostics: for each keypoint of kp (detected on this SIFT3D) the number of voxels its descriptor window accepts
  * (stats[2i]) and a checksum of their coordinates (stats[2i+1]); stats: host array of 2 * kp->slab.num. */
 int sift3d_amd_describe_window_stats(SIFT3D *const sift3d, const Keypoint_store *const kp, unsigned int *stats);
-/* Number of extrema candidates before orientation rejection in the last detect (diagnostics). */
+/* Number of extrema candidates before orientation rejection in the last single-GPU detect (diagnostics; a detect on several
+ * GPUs does not update it); with a mask set (sift3d_amd_set_mask): after masking. */
 long sift3d_amd_last_num_candidates(const SIFT3D *const sift3d);
 /* Stream on which this SIFT3D's kernels run (opaque hipStream_t); set before the first detect. */
 int sift3d_amd_set_stream(SIFT3D *const sift3d, void *hip_stream);
@@ -467,6 +468,33 @@ int sift3d_amd_detect_keypoints_typed(SIFT3D *const sift3d, const void *vol, int
 typedef struct { void *data; int dtype; int nx, ny, nz; double ux, uy, uz, slope, inter; } sift3d_amd_volume;
 int sift3d_amd_read_nii_native(const char *path, sift3d_amd_volume *out);
 void sift3d_amd_free_volume(sift3d_amd_volume *v);
+
+/* ---- region of interest: keypoints inside a voxel mask only ------------------------------------------------------------------
+ * mask: nx*ny*nz bytes, x fastest, of the volume's own dimensions; a voxel is inside the region iff its byte is non-zero (the
+ * whole byte).  A keypoint of octave o at octave coordinates (x, y, z) is kept iff
+ *     mask[(z << o) * ny * nx + (y << o) * nx + (x << o)] != 0
+ * -- the voxel of the input it sits on (octave o is the input decimated o times at (2x, 2y, 2z), imutil.c:1742-1768; keypoints
+ * map back with ldexp(1.0, o), sift.c:2616).  Nothing else changes: the pyramid, the DoG maxima and the peak thresholds are those
+ * of the whole volume, so the masked detect returns exactly the unmasked keypoint list with the masked-out records deleted,
+ * byte for byte and in the same order, and the descriptors of the survivors are those of the unmasked run.
+ * Masked-out candidates are removed BEFORE orientation assignment (that, and the descriptors never computed, is the saving):
+ *  - sift3d_amd_last_num_candidates reports the count after masking (single GPU; it is not updated by a multi-GPU detect,
+ *    whose ranks do not mask: see below);
+ *  - a NaN gradient in the orientation window of a masked-out candidate no longer fails the call (the reference fails at
+ *    sift.c:1430): a masked background stops being fatal.
+ * on_device: the mask lies in HBM and is read in place, else it is uploaded through a staging buffer that is released again.
+ * Any address will do; a device mask that is 16-byte aligned (every allocation is; an offset view of one may not be) is read
+ * 16 bytes per lane, any other a byte per lane -- the same bits, several times slower for that one pass over the mask.
+ * The mask is packed to one bit per voxel of every octave once, here (about n/7 bytes stay with the struct; the caller's
+ * buffer is not referenced after the call returns), and stays in force for every following SIFT3D_detect_keypoints,
+ * sift3d_amd_detect_keypoints_dev and sift3d_amd_detect_keypoints_typed on the struct, the verbatim pass of non-finite volumes
+ * included, until it is replaced or cleared (mask == NULL; the dimensions are then ignored).  A detect on a volume of other
+ * dimensions fails with a message naming both; bad arguments fail and leave a mask already set in force.  copy_SIFT3D copies
+ * the mask, cleanup_SIFT3D frees it.  sift3d_amd_plan, the descriptor entry points, the dense path and the matcher do not look
+ * at it.  With several GPUs (SIFT3D_NGPU > 1 / sift3d_amd_set_num_gpus) the gathered keypoint list is filtered on the host
+ * against the same bits: the same result, without the saving. */
+int sift3d_amd_set_mask(SIFT3D *const sift3d, const unsigned char *mask, int on_device, int nx, int ny, int nz);
+int sift3d_amd_have_mask(const SIFT3D *const sift3d);       /* 1: a mask is in force */
 
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)

@@ -123,7 +123,9 @@ int sift3d_amd_slab_get_info(const sift3d_amd_slab *sl, sift3d_amd_slab_info *in
 
 /* SIFT3D_detect_keypoints for this rank's slab: `vol` = base slices [z0, z1) (x fastest, nx*ny*(z1-z0) floats),
  * in HBM when on_device, else in host memory.  kp receives the keypoints whose centre lies in this rank's part
- * of each octave, in the reference order; kp->nx,ny,nz are the GLOBAL dims.  Collective: all ranks call it. */
+ * of each octave, in the reference order; kp->nx,ny,nz are the GLOBAL dims.  Collective: all ranks call it.
+ * A region of interest (sift3d_amd_set_mask, sift3d_amd.h) does not apply here: the slab API takes no SIFT3D struct after
+ * sift3d_amd_slab_create, and the ranks return every keypoint of their slab; filter the lists by the rule given there. */
 int sift3d_amd_slab_detect(sift3d_amd_slab *sl, const float *vol, int on_device, Keypoint_store *kp);
 /* SIFT3D_extract_descriptors for keypoints of this rank (normally the list detect returned).  desc may be NULL
  * (records stay in HBM); *d_desc (optional) = device pointer to the 776-float records.  Not collective. */

@@ -166,6 +166,26 @@ def detect_keypoints_typed(L: C.CDLL, sift3d, vol, kp, units=(1.0, 1.0, 1.0), sl
                                                nx, ny, nz, units[0], units[1], units[2], slope, inter, C.byref(kp))
 
 
+def set_mask(L: C.CDLL, sift3d, mask, shape=None) -> int:
+    """sift3d_amd_set_mask: keypoints of the following detects on ``sift3d`` inside the region of interest only.  ``mask``: a
+    numpy uint8 / bool array [nz, ny, nx] (host form; non-zero = inside), a device address -- e.g. a ``torch.uint8`` tensor's
+    ``data_ptr()`` -- with ``shape`` (nz, ny, nx) given (device form; any address, 16-byte aligned ones are packed with wide
+    loads, an offset view that is not with byte loads), or None to clear.  ``L`` must have been through
+    ``device.bind_extensions``.  Returns the C status."""
+    if mask is None:
+        return L.sift3d_amd_set_mask(C.byref(sift3d), None, 0, 0, 0, 0)
+    if isinstance(mask, np.ndarray):
+        if mask.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)) or mask.ndim != 3:
+            raise TypeError("a mask is a uint8 or bool array [nz, ny, nx]")
+        mask = np.ascontiguousarray(mask)                 # (a bool array stores one byte per element, 0 or 1)
+        nz, ny, nx = mask.shape
+        return L.sift3d_amd_set_mask(C.byref(sift3d), C.c_void_p(mask.ctypes.data), 0, nx, ny, nz)
+    if shape is None:
+        raise TypeError("a device address needs shape")
+    nz, ny, nx = shape
+    return L.sift3d_amd_set_mask(C.byref(sift3d), C.c_void_p(int(mask)), 1, nx, ny, nz)
+
+
 def volume_to_numpy(v: Volume) -> np.ndarray:
     """A copy of a ``Volume``'s elements as [nz, ny, nx] in their stored type."""
     dt = {code: d for d, code in TYPED_DTYPES.items()}[v.dtype]

@@ -137,6 +137,15 @@ typedef struct {
      * per 4 KB): [0] descriptor keys up, [1] keypoint coordinates down, [2] keypoint rotations down */
     void *h_stage[3];
     size_t h_stage_bytes[3];
+    /* region of interest (sift3d_amd_set_mask).  Only the packed form is kept: one bit per voxel of every octave (bit i <->
+     * linear voxel i, like the extrema bitmaps), the octaves one after the other in d_mask_bits -- about n / 7 bytes.  It
+     * belongs to the struct, not to the pyramid: a detect on other dimensions fails, it does not drop the mask. */
+    int mask_dims[3];                       /* nx, ny, nz of the mask; nx == 0: none */
+    int mask_noct;
+    int mask_odims[S3D_MAX_OCTAVES][3];     /* the octaves' dimensions, from a pyramid sized for mask_dims */
+    size_t mask_off[S3D_MAX_OCTAVES + 1];   /* first word of octave o; [mask_noct]: words in all */
+    unsigned long long *d_mask_bits;
+    unsigned long long *h_mask_bits;        /* host copy for the multi-GPU filter, fetched when first needed */
 } s3d_ctx;
 
 /* words of c->d_red.  The input's maximum sits directly in front of the counters, so that the copy that fetches the
@@ -206,9 +215,19 @@ static void ctx_free_pyramid(s3d_ctx *c)
     c->have_pyramid = 0;
 }
 
+static void ctx_clear_mask(s3d_ctx *c)
+{
+    dfree(&c->d_mask_bits);
+    free(c->h_mask_bits);
+    c->h_mask_bits = NULL;
+    c->mask_dims[0] = c->mask_dims[1] = c->mask_dims[2] = 0;
+    c->mask_noct = 0;
+}
+
 static void ctx_free_all(s3d_ctx *c)
 {
     ctx_free_pyramid(c);
+    ctx_clear_mask(c);
     dfree(&c->d_red); c->d_count = NULL; dfree(&c->d_mesh);
     dfree(&c->d_keys); dfree(&c->d_desc);
     c->desc_cap = 0;
@@ -435,6 +454,16 @@ int sift3d_amd_set_stream(SIFT3D *const sift3d, void *hip_stream)
 
 /* resize_SIFT3D (sift.c:938-986): octave count from the smallest dimension, pyramid metadata,
  * filter bank.  Voxel storage is allocated on the device by ctx_ensure_pyramid(). */
+/* octaves of an nx x ny x nz volume (sift.c:951-962); 0: too small */
+static int octaves_for(int nx, int ny, int nz)
+{
+    int mind = nx < ny ? nx : ny;
+    if (nz < mind) mind = nz;
+    const int last_octave = (int)log2((double)mind) - 3;
+    if (last_octave < 0) return 0;
+    return last_octave + 1 > S3D_MAX_OCTAVES ? S3D_MAX_OCTAVES : last_octave + 1;
+}
+
 static int resize_SIFT3D(SIFT3D *const sift3d, const int num_kp_levels)
 {
     const Image *const im = &sift3d->im;
@@ -443,15 +472,11 @@ static int resize_SIFT3D(SIFT3D *const sift3d, const int num_kp_levels)
     int num_octaves = 0;
     invalidate_device_pyramid(sift3d);
     if (im->nx > 0) {
-        int mind = im->nx < im->ny ? im->nx : im->ny;
-        if (im->nz < mind) mind = im->nz;
-        const int last_octave = (int)log2((double)mind) - 3;
-        if (last_octave < 0) {
+        num_octaves = octaves_for(im->nx, im->ny, im->nz);
+        if (num_octaves == 0) {
             S3D_MSG("resize_SIFT3D: input image is too small: must have at least 8 voxels in each dimension \n");
             return SIFT3D_FAILURE;
         }
-        num_octaves = last_octave + 1;
-        if (num_octaves > S3D_MAX_OCTAVES) num_octaves = S3D_MAX_OCTAVES;
     }
     if (s3d_resize_pyramid(im, -1, (unsigned)num_kp_levels, num_gpyr_levels, 0, (unsigned)num_octaves,
                            &sift3d->gpyr, 0) ||
@@ -691,7 +716,14 @@ static int extrema_octave(SIFT3D *const sift3d, s3d_ctx *c, int o, s3d_stream es
     const size_t n = c->level_elems[o];
     float *const *lp = &c->d_level[o * L];
     const size_t nwords = (n + 63) / 64;
+    const unsigned long long *mw = NULL;                 /* the octave's region-of-interest words (sift3d_amd_set_mask) */
     int fused = 1;                                       /* all keypoint levels in one pass over the GSS levels */
+    if (c->mask_dims[0]) {
+        /* ANDed into the words the compaction loads: candidates outside the region never reach the orientation step */
+        if (o >= c->mask_noct || c->mask_odims[o][0] != lv->nx || c->mask_odims[o][1] != lv->ny || c->mask_odims[o][2] != lv->nz)
+            API_FAIL("sift3d_amd: the mask's octave %d does not have the pyramid's dimensions", o);
+        mw = c->d_mask_bits + c->mask_off[o];
+    }
     if (nkp <= S3D_FUSED_KP_MAX && !c->verbatim) {
         unsigned long long *bits[S3D_FUSED_KP_MAX];
         for (int ks = 1; ks <= nkp; ks++) bits[ks - 1] = c->d_bits + (size_t)(ks - 1) * c->bits_words;
@@ -704,8 +736,8 @@ static int extrema_octave(SIFT3D *const sift3d, s3d_ctx *c, int o, s3d_stream es
             DEV(s3d_k_extrema_refilter((const float *const *)lp, nkp, lv->nx, lv->ny, lv->nz, 0, lv->nz, sift3d->peak_thresh,
                                        c->d_red + RED_DOGMAX, bits, es));
         if (fused == 0)                                 /* the nkp bitmaps in one count / scan / emit */
-            DEV(s3d_k_compact_bits_multi(bits[0], nwords, nkp, c->bits_words, 0u, c->d_cand_idx, c->d_cand_tag,
-                                         ((uint32_t)o << 8) | 1u, c->cand_cap, c->d_count, c->d_scratch, es));
+            DEV(s3d_k_compact_bits_multi_and(bits[0], nwords, nkp, c->bits_words, 0u, c->d_cand_idx, c->d_cand_tag,
+                                             ((uint32_t)o << 8) | 1u, c->cand_cap, c->d_count, c->d_scratch, mw, es));
     }
     if (nkp <= S3D_FUSED_KP_MAX && c->verbatim && !verbatim_per_level()) {
         /* a volume with non-finite voxels: the levels' DoG maxima as the reference's sequential scans leave them (s3d_k_seqmax,
@@ -723,16 +755,16 @@ static int extrema_octave(SIFT3D *const sift3d, s3d_ctx *c, int o, s3d_stream es
                                             c->d_red + RED_DOGMAX, bits, es);
         if (fused < 0) API_FAIL("sift3d_amd: extrema failed: %s", s3d_rt_last_error());
         if (fused == 0)
-            DEV(s3d_k_compact_bits_multi(bits[0], nwords, nkp, c->bits_words, 0u, c->d_cand_idx, c->d_cand_tag,
-                                         ((uint32_t)o << 8) | 1u, c->cand_cap, c->d_count, c->d_scratch, es));
+            DEV(s3d_k_compact_bits_multi_and(bits[0], nwords, nkp, c->bits_words, 0u, c->d_cand_idx, c->d_cand_tag,
+                                             ((uint32_t)o << 8) | 1u, c->cand_cap, c->d_count, c->d_scratch, mw, es));
     }
     for (int ks = 1; fused != 0 && ks <= nkp; ks++) {   /* DoG level ks <-> s = ks-1 ; uses GSS ks-1..ks+2 */
         /* the level's DoG maximum as the reference's sequential scan leaves it (a NaN in the level: s3d_k_seqmax) */
         DEV(s3d_k_seqmax(lp[ks], lp[ks + 1], n, c->d_red + RED_DOGMAX, c->d_red + RED_REC, es));
         DEV(s3d_k_extrema(lp[ks - 1], lp[ks], lp[ks + 1], lp[ks + 2], lv->nx, lv->ny, lv->nz, sift3d->peak_thresh,
                           c->d_red + RED_DOGMAX, c->d_bits, es));
-        DEV(s3d_k_compact_bits(c->d_bits, nwords, c->d_cand_idx, c->d_cand_tag, ((uint32_t)o << 8) | (uint32_t)ks,
-                               c->cand_cap, c->d_count, c->d_scratch, es));
+        DEV(s3d_k_compact_bits_multi_and(c->d_bits, nwords, 1, 0, 0u, c->d_cand_idx, c->d_cand_tag,
+                                         ((uint32_t)o << 8) | (uint32_t)ks, c->cand_cap, c->d_count, c->d_scratch, mw, es));
     }
     return SIFT3D_SUCCESS;
 }
@@ -1015,6 +1047,121 @@ int sift3d_amd_get_slab_info(const SIFT3D *const sift3d, int r, sift3d_amd_slab_
     return c ? s3d_mgpu_info(c->mgpu, r, info) : SIFT3D_FAILURE;
 }
 
+/* ---- region of interest (include/sift3d_amd.h) ---------------------------------------------------------------------------- */
+int sift3d_amd_set_mask(SIFT3D *const sift3d, const unsigned char *mask, int on_device, int nx, int ny, int nz)
+{
+    s3d_ctx *c;
+    Pyramid pyr;
+    Image im;
+    unsigned long long *d_bits = NULL;
+    void *d_stage = NULL;
+    const unsigned char *d_mask;
+    size_t off[S3D_MAX_OCTAVES + 1];
+    int odims[S3D_MAX_OCTAVES][3];
+    int noct, rc = SIFT3D_FAILURE;
+    if (sift3d == NULL) API_FAIL("sift3d_amd_set_mask: null argument");
+    if (mask == NULL) {                                    /* clear */
+        if ((c = sift_ctx(sift3d)) != NULL) ctx_clear_mask(c);
+        return SIFT3D_SUCCESS;
+    }
+    if (nx < 1 || ny < 1 || nz < 1) API_FAIL("sift3d_amd_set_mask: bad dimensions %d x %d x %d", nx, ny, nz);
+    if ((noct = octaves_for(nx, ny, nz)) == 0)
+        API_FAIL("sift3d_amd_set_mask: %d x %d x %d is too small for a detect: at least 8 voxels in each dimension", nx, ny, nz);
+    if (!sift3d->kernels.downsample_2 && !(sift3d->kernels.downsample_2 = ctx_new()))
+        API_FAIL("sift3d_amd: out of device contexts");
+    c = sift_ctx(sift3d);
+    /* the octaves' dimensions as the detect's pyramid will have them: from a pyramid sized by the same routine */
+    init_Pyramid(&pyr);
+    init_im(&im);
+    im.nx = nx; im.ny = ny; im.nz = nz; im.nc = 1;
+    im_default_stride(&im);
+    if (s3d_resize_pyramid(&im, 0, 1, 1, 0, (unsigned)noct, &pyr, 0)) {
+        cleanup_Pyramid(&pyr);
+        API_FAIL("sift3d_amd_set_mask: cannot size the pyramid");
+    }
+    off[0] = 0;
+    for (int o = 0; o < noct; o++) {
+        const Image *lv = pyr.levels + o;
+        odims[o][0] = lv->nx; odims[o][1] = lv->ny; odims[o][2] = lv->nz;
+        off[o + 1] = off[o] + ((size_t)lv->nx * lv->ny * lv->nz + 63) / 64;
+    }
+    cleanup_Pyramid(&pyr);
+    /* the new bitmaps are built beside the old ones: a failure leaves the mask that was set */
+    do {
+        const size_t n = (size_t)nx * ny * nz;
+        if (s3d_rt_malloc((void **)&d_bits, off[noct] * sizeof(unsigned long long))) break;
+        d_mask = mask;
+        if (!on_device) {                                  /* up through a staging buffer that goes again below */
+            if (s3d_rt_malloc(&d_stage, n) || s3d_rt_h2d(d_stage, mask, n, c->stream)) break;
+            d_mask = (const unsigned char *)d_stage;
+        }
+        int o;
+        for (o = 0; o < noct; o++)
+            if (s3d_k_mask_pack(d_mask, nx, ny, odims[o][0], odims[o][1], odims[o][2], o, d_bits + off[o], c->stream)) break;
+        if (o < noct || s3d_rt_sync(c->stream)) break;     /* the caller's mask and the staging buffer are free again */
+        rc = SIFT3D_SUCCESS;
+    } while (0);
+    if (d_stage) s3d_rt_free(d_stage);
+    if (rc != SIFT3D_SUCCESS) {
+        if (d_bits) s3d_rt_free(d_bits);
+        API_FAIL("sift3d_amd_set_mask: packing the mask failed: %s", s3d_rt_last_error());
+    }
+    ctx_clear_mask(c);
+    c->d_mask_bits = d_bits;
+    c->mask_dims[0] = nx; c->mask_dims[1] = ny; c->mask_dims[2] = nz;
+    c->mask_noct = noct;
+    memcpy(c->mask_off, off, sizeof(off));
+    memcpy(c->mask_odims, odims, sizeof(odims));
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_have_mask(const SIFT3D *const sift3d)
+{
+    const s3d_ctx *c = sift3d ? sift_ctx(sift3d) : NULL;
+    return c != NULL && c->mask_dims[0] != 0;
+}
+
+/* a detect on a volume of other dimensions than the mask's fails: the mask is not silently ignored */
+static int mask_check_dims(const SIFT3D *sift3d, int nx, int ny, int nz)
+{
+    const s3d_ctx *c = sift_ctx(sift3d);
+    if (c == NULL || c->mask_dims[0] == 0) return SIFT3D_SUCCESS;
+    if (c->mask_dims[0] != nx || c->mask_dims[1] != ny || c->mask_dims[2] != nz)
+        API_FAIL("sift3d_amd: the volume is %d x %d x %d but the mask set with sift3d_amd_set_mask is %d x %d x %d "
+                 "(set a mask of the volume's dimensions, or clear it with mask = NULL)", nx, ny, nz, c->mask_dims[0],
+                 c->mask_dims[1], c->mask_dims[2]);
+    return SIFT3D_SUCCESS;
+}
+
+/* Several GPUs: the Z-slab ranks do not look at the mask, so the gathered global list is filtered here, on the host, against
+ * a host copy of the packed bitmaps -- the same bits, hence the same survivors in the same order; without the saving. */
+static int mask_filter_store(s3d_ctx *c, Keypoint_store *const kp)
+{
+    size_t kept = 0;
+    if (c->mask_dims[0] == 0) return SIFT3D_SUCCESS;
+    if (c->h_mask_bits == NULL) {
+        const size_t bytes = c->mask_off[c->mask_noct] * sizeof(unsigned long long);
+        if ((c->h_mask_bits = (unsigned long long *)malloc(bytes)) == NULL) API_FAIL("sift3d_amd: out of memory");
+        if (s3d_rt_d2h(c->h_mask_bits, c->d_mask_bits, bytes, c->stream) || s3d_rt_sync(c->stream)) {
+            free(c->h_mask_bits);
+            c->h_mask_bits = NULL;
+            API_FAIL("sift3d_amd: fetching the mask failed: %s", s3d_rt_last_error());
+        }
+    }
+    for (size_t i = 0; i < kp->slab.num; i++) {
+        const Keypoint *key = kp->buf + i;
+        const int o = key->o, x = (int)key->xd, y = (int)key->yd, z = (int)key->zd;
+        if (o < 0 || o >= c->mask_noct || x < 0 || y < 0 || z < 0 || x >= c->mask_odims[o][0] || y >= c->mask_odims[o][1] ||
+            z >= c->mask_odims[o][2])
+            API_FAIL("sift3d_amd: keypoint %zu lies outside the mask's octave %d", i, o);
+        const size_t idx = (size_t)x + (size_t)c->mask_odims[o][0] * ((size_t)y + (size_t)c->mask_odims[o][1] * (size_t)z);
+        if (!((c->h_mask_bits[c->mask_off[o] + (idx >> 6)] >> (idx & 63)) & 1ull)) continue;
+        if (kept != i && copy_Keypoint(key, kp->buf + kept)) return SIFT3D_FAILURE;
+        kept++;
+    }
+    return resize_Keypoint_store(kp, kept);
+}
+
 static int detect_single(SIFT3D *const sift3d, const float *host_dense, const float *d_vol, int nx, int ny, int nz,
                          double ux, double uy, double uz, Keypoint_store *const kp, const s3d_typed_src *ts);
 
@@ -1037,10 +1184,15 @@ int SIFT3D_detect_keypoints(SIFT3D *const sift3d, const Image *const im, Keypoin
     }
     if (mgpu_for(sift3d) > 1) {                            /* Z-slabs over several GPUs (s3d_host_slab.c) */
         s3d_ctx *c = sift_ctx(sift3d);
+        if (mask_check_dims(sift3d, im->nx, im->ny, im->nz)) {
+            free(dense);
+            return SIFT3D_FAILURE;
+        }
         c->have_pyramid = 0;
         rc = set_im_meta(sift3d, im->nx, im->ny, im->nz, im->ux, im->uy, im->uz);
         if (rc == SIFT3D_SUCCESS)
             rc = s3d_mgpu_detect(&c->mgpu, sift3d, src, im->nx, im->ny, im->nz, im->ux, im->uy, im->uz, kp);
+        if (rc == SIFT3D_SUCCESS) rc = mask_filter_store(c, kp);      /* the descriptors then describe the filtered store */
         free(dense);
         if (rc) return SIFT3D_FAILURE;
         c->have_pyramid = c->pyramid_on_slabs = 1;
@@ -1063,6 +1215,7 @@ static int detect_single(SIFT3D *const sift3d, const float *host_dense, const fl
                          double ux, double uy, double uz, Keypoint_store *const kp, const s3d_typed_src *ts)
 {
     int rc = SIFT3D_FAILURE;
+    if (mask_check_dims(sift3d, nx, ny, nz)) return SIFT3D_FAILURE;
     for (int verbatim = 0; verbatim < 2; verbatim++) {
         s3d_ctx *c;
         if (!sift3d->kernels.downsample_2 && !(sift3d->kernels.downsample_2 = ctx_new()))
@@ -1499,12 +1652,26 @@ int copy_SIFT3D(const SIFT3D *const src, SIFT3D *const dst)
         set_num_kp_levels_SIFT3D(dst, (unsigned)src->gpyr.num_kp_levels))
         return SIFT3D_FAILURE;
     dst->dense_rotate = src->dense_rotate;
+    if (sc != NULL && sc->mask_dims[0]) {                 /* the region of interest goes with the struct, device to device */
+        s3d_ctx *dc;
+        const size_t bytes = sc->mask_off[sc->mask_noct] * sizeof(unsigned long long);
+        if (!(dst->kernels.downsample_2 = ctx_new())) API_FAIL("sift3d_amd: out of device contexts");
+        dc = sift_ctx(dst);
+        dc->stream = sc->stream;
+        DEV(s3d_rt_malloc((void **)&dc->d_mask_bits, bytes));
+        DEV(s3d_rt_d2d(dc->d_mask_bits, sc->d_mask_bits, bytes, dc->stream));
+        DEV(s3d_rt_sync(dc->stream));
+        memcpy(dc->mask_dims, sc->mask_dims, sizeof(dc->mask_dims));
+        memcpy(dc->mask_odims, sc->mask_odims, sizeof(dc->mask_odims));
+        memcpy(dc->mask_off, sc->mask_off, sizeof(dc->mask_off));
+        dc->mask_noct = sc->mask_noct;
+    }
     if (sc == NULL || sc->d_im == NULL || src->im.nx <= 0 || sc->pyramid_on_slabs)
         return SIFT3D_SUCCESS;                            /* no image yet (a multi-GPU pyramid is not copied: parameters only) */
     {
         s3d_ctx *dc;
         const int L = src->gpyr.num_levels;
-        if (!(dst->kernels.downsample_2 = ctx_new())) API_FAIL("sift3d_amd: out of device contexts");
+        if (!dst->kernels.downsample_2 && !(dst->kernels.downsample_2 = ctx_new())) API_FAIL("sift3d_amd: out of device contexts");
         dc = sift_ctx(dst);
         dc->stream = sc->stream;
         if (ctx_base(dc)) return SIFT3D_FAILURE;

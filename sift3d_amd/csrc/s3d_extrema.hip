@@ -460,14 +460,14 @@ __device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned *total)
  * b works on block b % nb of segment b / nb, so that the block counters -- and with them the output -- are in segment-major
  * order (level, then voxel index: the reference's scan order) and one count / scan / emit triple serves all levels. */
 __global__ void __launch_bounds__(256)
-k_cb_count(const unsigned long long *__restrict__ bits, size_t nwords, unsigned *__restrict__ block_count, unsigned nb,
-           size_t seg_stride)
+k_cb_count(const unsigned long long *__restrict__ bits, const unsigned long long *__restrict__ band, size_t nwords,
+           unsigned *__restrict__ block_count, unsigned nb, size_t seg_stride)
 {
     bits += (size_t)(blockIdx.x / nb) * seg_stride;
     const size_t w0 = (size_t)(blockIdx.x % nb) * CB_WORDS_PER_BLOCK + (size_t)threadIdx.x * CB_WORDS_PER_THREAD;
     unsigned c = 0;
     for (int i = 0; i < CB_WORDS_PER_THREAD; i++)
-        if (w0 + i < nwords) c += (unsigned)__popcll(bits[w0 + i]);
+        if (w0 + i < nwords) c += (unsigned)__popcll(band ? bits[w0 + i] & band[w0 + i] : bits[w0 + i]);
     unsigned total;
     block_scan_incl(c, &total);
     if (threadIdx.x == 0) block_count[blockIdx.x] = total;
@@ -490,8 +490,8 @@ __global__ void __launch_bounds__(256) k_cb_scan(unsigned *__restrict__ block_co
 }
 
 __global__ void __launch_bounds__(256)
-k_cb_emit(const unsigned long long *__restrict__ bits, size_t nwords, const unsigned *__restrict__ block_off,
-          unsigned *__restrict__ out_idx, unsigned *__restrict__ out_tag, unsigned tag, unsigned capacity,
+k_cb_emit(const unsigned long long *__restrict__ bits, const unsigned long long *__restrict__ band, size_t nwords,
+          const unsigned *__restrict__ block_off, unsigned *__restrict__ out_idx, unsigned *__restrict__ out_tag, unsigned tag, unsigned capacity,
           unsigned idx_base, unsigned nb, size_t seg_stride)
 {
     const unsigned seg = blockIdx.x / nb;
@@ -501,7 +501,7 @@ k_cb_emit(const unsigned long long *__restrict__ bits, size_t nwords, const unsi
     unsigned long long w[CB_WORDS_PER_THREAD];
     unsigned c = 0;
     for (int i = 0; i < CB_WORDS_PER_THREAD; i++) {
-        w[i] = (w0 + i < nwords) ? bits[w0 + i] : 0ull;
+        w[i] = (w0 + i < nwords) ? (band ? bits[w0 + i] & band[w0 + i] : bits[w0 + i]) : 0ull;
         c += (unsigned)__popcll(w[i]);
     }
     unsigned total;
@@ -521,10 +521,6 @@ k_cb_emit(const unsigned long long *__restrict__ bits, size_t nwords, const unsi
     }
 }
 
-extern "C" int s3d_k_compact_bits_multi(const unsigned long long *d_bits, size_t nwords, int nseg, size_t seg_stride,
-                                        uint32_t idx_base, uint32_t *d_idx, uint32_t *d_tag, uint32_t tag, uint32_t capacity,
-                                        uint32_t *d_count, uint32_t *d_scratch, s3d_stream stream);
-
 extern "C" int s3d_k_compact_bits(const unsigned long long *d_bits, size_t nwords, uint32_t *d_idx, uint32_t *d_tag,
                                   uint32_t tag, uint32_t capacity, uint32_t *d_count, uint32_t *d_scratch,
                                   s3d_stream stream)
@@ -537,7 +533,8 @@ extern "C" int s3d_k_compact_bits_base(const unsigned long long *d_bits, size_t 
                                        uint32_t *d_idx, uint32_t *d_tag, uint32_t tag, uint32_t capacity,
                                        uint32_t *d_count, uint32_t *d_scratch, s3d_stream stream)
 {
-    return s3d_k_compact_bits_multi(d_bits, nwords, 1, 0, idx_base, d_idx, d_tag, tag, capacity, d_count, d_scratch, stream);
+    return s3d_k_compact_bits_multi_and(d_bits, nwords, 1, 0, idx_base, d_idx, d_tag, tag, capacity, d_count, d_scratch, NULL,
+                                        stream);
 }
 
 /* nseg bitmaps of nwords words, seg_stride words apart, appended one after the other with tags tag, tag + 1, ...:
@@ -546,16 +543,122 @@ extern "C" int s3d_k_compact_bits_multi(const unsigned long long *d_bits, size_t
                                         uint32_t idx_base, uint32_t *d_idx, uint32_t *d_tag, uint32_t tag, uint32_t capacity,
                                         uint32_t *d_count, uint32_t *d_scratch, s3d_stream stream)
 {
+    return s3d_k_compact_bits_multi_and(d_bits, nwords, nseg, seg_stride, idx_base, d_idx, d_tag, tag, capacity, d_count,
+                                        d_scratch, NULL, stream);
+}
+
+/* The same over bits[w] & d_and[w]: d_and (nwords words, or NULL: no AND) is one bitmap shared by all segments -- the
+ * region of interest of the octave (s3d_k_mask_pack).  The AND is taken where the count and the emit kernels load the word:
+ * two more reads of one bit per voxel, no launch, and the extrema bitmaps stay what the extrema kernels wrote. */
+extern "C" int s3d_k_compact_bits_multi_and(const unsigned long long *d_bits, size_t nwords, int nseg, size_t seg_stride,
+                                            uint32_t idx_base, uint32_t *d_idx, uint32_t *d_tag, uint32_t tag,
+                                            uint32_t capacity, uint32_t *d_count, uint32_t *d_scratch,
+                                            const unsigned long long *d_and, s3d_stream stream)
+{
     hipStream_t st = (hipStream_t)stream;
     if (nwords == 0 || nseg < 1) return S3D_OK;
     const unsigned nb = s3d_div_up(nwords, CB_WORDS_PER_BLOCK);
     const unsigned nbt = nb * (unsigned)nseg;
-    hipLaunchKernelGGL(k_cb_count, dim3(nbt), dim3(256), 0, st, d_bits, nwords, d_scratch, nb, seg_stride);
+    hipLaunchKernelGGL(k_cb_count, dim3(nbt), dim3(256), 0, st, d_bits, d_and, nwords, d_scratch, nb, seg_stride);
     S3D_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_cb_scan, dim3(1), dim3(256), 0, st, d_scratch, nbt, d_count);
     S3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_cb_emit, dim3(nbt), dim3(256), 0, st, d_bits, nwords, d_scratch, d_idx, d_tag, tag, capacity,
+    hipLaunchKernelGGL(k_cb_emit, dim3(nbt), dim3(256), 0, st, d_bits, d_and, nwords, d_scratch, d_idx, d_tag, tag, capacity,
                        idx_base, nb, seg_stride);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* ---- region of interest: a byte mask of the input volume as one bit per voxel of an octave ---------------------------------
+ * Octave o is the input decimated o times by taking voxel (2x, 2y, 2z) (im_downsample_2x, imutil.c:1742-1768), and a keypoint
+ * of octave o maps back to the input by ldexp(1.0, o) (sift.c:2616): voxel (x, y, z) of the octave IS voxel
+ * (x << o, y << o, z << o) of the input.  Bit i = x + onx * (y + ony * z) of the octave's bitmap is set iff that byte of the
+ * mask is non-zero (the whole byte, not bit 0). */
+
+/* 16 bytes at a 16-byte aligned address; the emulator build has no uint4 */
+#if defined(__clang__)
+typedef unsigned s3d_u4 __attribute__((ext_vector_type(4)));
+#else
+struct s3d_u4 { unsigned x, y, z, w; };
+#endif
+
+/* bit j of the result <-> byte j of d is non-zero.  Per byte: (low seven bits + 0x7f) carries into bit 7 iff one of them
+ * is set, OR the byte's own bit 7; the four flags at bits 7, 15, 23, 31 are then gathered by one multiplication (the sixteen
+ * partial products land on sixteen different bits: no carries). */
+__device__ __forceinline__ unsigned mask_nz4(unsigned d)
+{
+    const unsigned f = ((((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u) >> 7;
+    return ((f * 0x00204081u) >> 21) & 0xfu;
+}
+
+/* Octave 0, the case that costs (the whole mask is read: 128 MiB at 512^3): a lane takes 16 consecutive bytes in one load
+ * and makes 16 bits of them, two exchanges inside each group of four lanes put the 64-bit word together, and the group's
+ * first lane stores it -- every word once, by one lane.  The last lanes of the volume read byte by byte.  d_mask is 16-byte
+ * aligned. */
+__global__ void __launch_bounds__(256)
+k_mask_pack16(const unsigned char *__restrict__ mask, size_t n, size_t nwords, unsigned long long *__restrict__ bits)
+{
+    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;      /* 16-byte group */
+    const size_t i0 = g * 16u;
+    unsigned v = 0;
+    if (i0 + 16u <= n) {
+        const s3d_u4 q = *reinterpret_cast<const s3d_u4 *>(mask + i0);
+        v = mask_nz4(q.x) | mask_nz4(q.y) << 4 | mask_nz4(q.z) << 8 | mask_nz4(q.w) << 12;
+    } else if (i0 < n) {
+        for (unsigned j = 0; j < (unsigned)(n - i0); j++) v |= (mask[i0 + j] != 0 ? 1u : 0u) << j;
+    }
+    const unsigned q4 = threadIdx.x & 3u;
+    const unsigned a = __shfl_xor(v, 1);
+    const unsigned pair = (q4 & 1u) ? (a | v << 16) : (v | a << 16);          /* both lanes of a pair hold its 32 bits */
+    const unsigned b = __shfl_xor(pair, 2);
+    if (q4 == 0 && (g >> 2) < nwords) bits[g >> 2] = (unsigned long long)pair | (unsigned long long)b << 32;
+}
+
+/* Any shift (and octave 0 of a mask that is not 16-byte aligned): a lane per voxel of the octave reads its one byte, the
+ * wave's ballot is the word.  Octave o touches 1/8^o of the bytes.  LINEAR: the octave is the mask itself (shift 0, the
+ * mask's own rows and planes), voxel i is byte i -- no coordinates to take apart. */
+template <bool LINEAR>
+__global__ void __launch_bounds__(256)
+k_mask_pack(const unsigned char *__restrict__ mask, unsigned nx, unsigned ny, unsigned onx, unsigned ony, size_t n,
+            unsigned shift, unsigned long long *__restrict__ bits)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    int pred = 0;
+    if (LINEAR) {
+        if (i < n) pred = mask[i] != 0;
+    } else if (i < n) {
+        const size_t oplane = (size_t)onx * ony;
+        const size_t z = i / oplane;
+        const size_t rem = i - z * oplane;
+        const size_t y = rem / onx;
+        const size_t x = rem - y * onx;
+        pred = mask[((z << shift) * ny + (y << shift)) * nx + (x << shift)] != 0;
+    }
+    const unsigned long long m = __ballot(pred);
+    if ((threadIdx.x & 63u) == 0 && i < ((n + 63u) & ~(size_t)63u)) bits[i >> 6] = m;
+}
+
+extern "C" int s3d_k_mask_pack(const unsigned char *d_mask, int nx, int ny, int onx, int ony, int onz, int shift,
+                               unsigned long long *d_bits, s3d_stream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (d_mask == NULL || d_bits == NULL) S3D_FAIL("null pointer");
+    if (nx < 1 || ny < 1 || onx < 1 || ony < 1 || onz < 1 || shift < 0 || shift >= S3D_MAX_OCTAVES) S3D_FAIL("bad arguments");
+    /* the octave's last voxel lies inside the mask's rows and planes (its z extent is the caller's) */
+    if ((((long long)onx - 1) << shift) >= nx || (((long long)ony - 1) << shift) >= ny) S3D_FAIL("octave larger than the mask");
+    const size_t n = (size_t)onx * ony * onz;
+    const size_t nwords = (n + 63) / 64;
+    if (s3d_div_up(n, 256) > 0x7fffffffu) S3D_FAIL("octave too large");
+    const bool linear = shift == 0 && onx == nx && ony == ny;
+    if (linear && ((uintptr_t)d_mask & 15u) == 0) {
+        hipLaunchKernelGGL(k_mask_pack16, dim3(s3d_div_up(nwords * 4, 256)), dim3(256), 0, st, d_mask, n, nwords, d_bits);
+    } else if (linear) {
+        hipLaunchKernelGGL(k_mask_pack<true>, dim3(s3d_div_up(n, 256)), dim3(256), 0, st, d_mask, (unsigned)nx, (unsigned)ny,
+                           (unsigned)onx, (unsigned)ony, n, (unsigned)shift, d_bits);
+    } else {
+        hipLaunchKernelGGL(k_mask_pack<false>, dim3(s3d_div_up(n, 256)), dim3(256), 0, st, d_mask, (unsigned)nx, (unsigned)ny,
+                           (unsigned)onx, (unsigned)ony, n, (unsigned)shift, d_bits);
+    }
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }

@@ -35,6 +35,11 @@ def bind_extensions(L: C.CDLL) -> None:
     L.sift3d_amd_read_nii_native.argtypes = [C.c_char_p, P(abi.Volume)]
     L.sift3d_amd_free_volume.argtypes = [P(abi.Volume)]
     L.sift3d_amd_free_volume.restype = None
+    # (an older build of the library, loaded through SIFT3D_AMD_LIB for an A/B run, has no masks: nothing is bound for it, and
+    # a caller that asks for one fails on the missing symbol)
+    if hasattr(L, "sift3d_amd_set_mask"):
+        L.sift3d_amd_set_mask.argtypes = [P(abi.SIFT3D), _vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.sift3d_amd_have_mask.argtypes = [P(abi.SIFT3D)]
 
 
 class DeviceLib:
@@ -74,6 +79,13 @@ class DeviceLib:
         L.s3d_k_sep_fir_div_typed_eligible.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
         L.s3d_k_sep_fir_div_typed.argtypes = [_vp, C.c_int, C.c_double, C.c_double, _vp, _vp, C.c_int, C.c_int, C.c_int,
                                               _f32p, _f32p, C.c_int, _vp, _vp]
+        # region of interest: (bits, nwords, nseg, seg_stride, idx_base, idx, tag, tag0, capacity, count, scratch[, and], stream)
+        L.s3d_k_compact_bits_multi.argtypes = [_vp, C.c_size_t, C.c_int, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32,
+                                               C.c_uint32, _vp, _vp, _vp]
+        if hasattr(L, "s3d_k_mask_pack"):                 # (absent from builds older than the region of interest, see above)
+            L.s3d_k_compact_bits_multi_and.argtypes = [_vp, C.c_size_t, C.c_int, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32,
+                                                       C.c_uint32, _vp, _vp, _vp, _vp]
+            L.s3d_k_mask_pack.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -153,6 +165,21 @@ class DeviceLib:
         """*d_max = max |converted d_src[i]| (s3d_k_absmax_typed)."""
         self.check(self.L.s3d_k_absmax_typed(_vp(d_src), abi.TYPED_DTYPES[np.dtype(dtype)], n, slope, inter, _vp(d_max),
                                              _vp(stream)), "s3d_k_absmax_typed")
+
+    # --- region of interest ------------------------------------------------------------------------------
+    def mask_pack(self, d_mask: int, nx: int, ny: int, odims, shift: int, d_bits: int, stream=None) -> None:
+        """One bit per voxel of the octave ``odims`` = (onx, ony, onz) from the byte mask of an nx x ny x . volume
+        (s3d_k_mask_pack): ceil(onx * ony * onz / 64) words at d_bits."""
+        self.check(self.L.s3d_k_mask_pack(_vp(d_mask), nx, ny, odims[0], odims[1], odims[2], shift, _vp(d_bits), _vp(stream)),
+                   "s3d_k_mask_pack")
+
+    def compact_bits_multi_and(self, d_bits: int, nwords: int, nseg: int, seg_stride: int, idx_base: int, d_idx: int,
+                               d_tag: int, tag: int, capacity: int, d_count: int, d_scratch: int, d_and: int | None,
+                               stream=None) -> None:
+        """s3d_k_compact_bits_multi over d_bits[w] & d_and[w]; d_and None: no AND."""
+        self.check(self.L.s3d_k_compact_bits_multi_and(_vp(d_bits), nwords, nseg, seg_stride, idx_base, _vp(d_idx), _vp(d_tag),
+                                                       tag, capacity, _vp(d_count), _vp(d_scratch), _vp(d_and), _vp(stream)),
+                   "s3d_k_compact_bits_multi_and")
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
