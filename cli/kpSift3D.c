@@ -1,11 +1,14 @@
 /* kpSift3D -- keypoints and descriptors of one volume, on the MI355X.
  *
  * Same command line, outputs and messages as the reference program (cli/kpSift3D.c:1-228):
- *     kpSift3D [SIFT3D options] [--keys keys.csv] [--desc desc.csv] [--draw points.nii] [--mask mask.nii] image.nii
+ *     kpSift3D [SIFT3D options] [--keys keys.csv] [--desc desc.csv] [--draw points.nii] [--mask mask.nii] [--max_keypoints N]
+ *              image.nii
  * linked against libsift3d_amd.so instead of libsift3D/libimutil.  Every call below is the reference's
  * API; detection and description run as HIP kernels, the rest is host C.  --mask is this program's own: keypoints inside a
- * region of interest only (sift3d_amd_set_mask).
+ * region of interest only (sift3d_amd_set_mask); so is --max_keypoints: the N strongest keypoints only
+ * (sift3d_amd_set_max_keypoints).
  */
+#include <errno.h>
 #include <getopt.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -34,6 +37,8 @@ static const char usage[] =
     "At least one of the output options must be specified. \n"
     " --mask [filename] \n"
     "       Keeps the keypoints on non-zero voxels of this image (same dimensions) only. \n"
+    " --max_keypoints [N] \n"
+    "       Keeps the N keypoints of largest |DoG| response only (0: all). \n"
     "\n";
 
 static void complain(const char *msg)
@@ -101,17 +106,19 @@ static unsigned char *read_mask(const char *path, int nx, int ny, int nz)
 
 int main(int argc, char *argv[])
 {
-    enum { OPT_KEYS = 'a', OPT_DESC, OPT_DRAW, OPT_MASK };
+    enum { OPT_KEYS = 'a', OPT_DESC, OPT_DRAW, OPT_MASK, OPT_MAXKP };
     static const struct option outputs[] = {{"keys", required_argument, NULL, OPT_KEYS},
                                             {"desc", required_argument, NULL, OPT_DESC},
                                             {"draw", required_argument, NULL, OPT_DRAW},
                                             {"mask", required_argument, NULL, OPT_MASK},
+                                            {"max_keypoints", required_argument, NULL, OPT_MAXKP},
                                             {0, 0, 0, 0}};
     SIFT3D sift3d;
     Image im;
     Keypoint_store kp;
     SIFT3D_Descriptor_store desc;
     const char *keys_path = NULL, *desc_path = NULL, *draw_path = NULL, *mask_path = NULL;
+    long max_keypoints = 0;
 
     switch (parse_gnu(argc, argv)) {
     case SIFT3D_HELP:
@@ -135,6 +142,15 @@ int main(int argc, char *argv[])
         else if (c == OPT_DESC) desc_path = optarg;
         else if (c == OPT_DRAW) draw_path = optarg;
         else if (c == OPT_MASK) mask_path = optarg;
+        else if (c == OPT_MAXKP) {
+            char *end;
+            errno = 0;
+            max_keypoints = strtol(optarg, &end, 10);
+            if (errno || end == optarg || *end != '\0' || max_keypoints < 0) {
+                complain("--max_keypoints takes a non-negative integer.");
+                return 1;
+            }
+        }
         else return 1;
     }
     if (!keys_path && !desc_path && !draw_path) {
@@ -167,6 +183,10 @@ int main(int argc, char *argv[])
             return 1;
         }
         free(mask);
+    }
+    if (sift3d_amd_set_max_keypoints(&sift3d, max_keypoints)) {
+        complain_bug("Failed to set the keypoint budget.");
+        return 1;
     }
     if (SIFT3D_detect_keypoints(&sift3d, &im, &kp)) {
         complain_bug("Failed to detect keypoints.");

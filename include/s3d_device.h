@@ -309,6 +309,23 @@ void s3d_k_set_orient_chunk(uint32_t n);
 int s3d_k_compact_keys(const s3d_pyramid_desc *pyr, const uint32_t *d_idx, const uint32_t *d_tag,
                        const float *d_R, const uint32_t *d_keep, uint32_t num, int32_t *d_xyzos,
                        float *d_R_out, uint32_t *d_num_out, uint32_t *d_scratch, s3d_stream stream);
+/* Keypoint budget (extension, sift3d_amd_set_max_keypoints).  d_strength[i] = |D| of candidate i's own voxel, D the DoG voxel
+ * as the reference stores it (build_dog, sift.c:1052-1071: one f32 subtraction of GSS levels s + 1 and s), i.e.
+ * |d_level[o*L + k + 1][idx] - d_level[o*L + k][idx]| with tag = o<<8 | k, k = s - first_level as for s3d_k_orient: the voxel
+ * sift3d_amd_download_pyramid(.., 1) returns, never stored on the device.  d_keep (may be NULL: every candidate): entries with
+ * d_keep[i] == 0 are not written.  The caller vouches for idx < the level's voxels and k + 1 < num_levels. */
+int s3d_k_key_strength(const s3d_pyramid_desc *pyr, const uint32_t *d_idx, const uint32_t *d_tag, const uint32_t *d_keep,
+                       uint32_t num, float *d_strength, s3d_stream stream);
+/* Clears d_keep[i] of every kept entry (d_keep[i] != 0) that is not among the `budget` (> 0) kept entries of largest
+ * d_strength; equal strengths go to the lower i.  Exact and deterministic: a radix select over the bit patterns of the
+ * non-negative strengths (the sign bit is ignored; no NaNs) with integer atomics only, then an ordered count over the entries
+ * equal to the threshold.  No more kept entries than `budget`: d_keep is left untouched -- decided on the device, the host
+ * need not know the number (budget >= num returns without a launch).  Entries with d_keep[i] == 0 are never read.  Eight
+ * launches ordered by the stream, none waits for another workgroup.  d_scratch: s3d_k_select_scratch_bytes(num) bytes,
+ * owned by the call until it has run. */
+size_t s3d_k_select_scratch_bytes(uint32_t num);
+int s3d_k_select_strongest(const float *d_strength, uint32_t *d_keep, uint32_t num, uint32_t budget, void *d_scratch,
+                           s3d_stream stream);
 
 /* One record per keypoint for the descriptor kernel; the scalar set-up mirrors
  * extract_descrip (sift.c:1845-1851) and is done on the host in the same float arithmetic. */

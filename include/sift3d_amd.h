@@ -496,6 +496,37 @@ void sift3d_amd_free_volume(sift3d_amd_volume *v);
 int sift3d_amd_set_mask(SIFT3D *const sift3d, const unsigned char *mask, int on_device, int nx, int ny, int nz);
 int sift3d_amd_have_mask(const SIFT3D *const sift3d);       /* 1: a mask is in force */
 
+/* ---- keypoint budget: the n strongest keypoints only -----------------------------------------------------------------------------
+ * The strength of a keypoint (x, y, z, o, s) is fabsf(D) as an f32, D the voxel (x, y, z) of DoG level (o, s) as the reference
+ * stores it: the single-rounded f32 difference of the two Gaussian levels either side (build_dog, sift.c:1052-1071) -- the voxel
+ * sift3d_amd_download_pyramid(sift3d, 1) returns in sift3d->dog.  (The DoG is not stored on the device; the kernel subtracts.)
+ * With a budget n > 0 set, a detect returns exactly the list the same detect returns without one, with every record deleted
+ * except the n of largest strength: equal strengths go to the record that comes earlier in that list, the survivors keep the
+ * reference's order and are byte for byte the records of the unbudgeted run (R and sd included), and so are their descriptors.
+ * A list of no more than n records comes back unchanged.  n = 0, the default, is no budget: nothing is launched for it.
+ * Order of steps: a mask (sift3d_amd_set_mask) removes candidates first, orientation assignment then decides on all that remain
+ * as it does without a budget, and the budget ranks the survivors of both.  So the budget never changes which calls fail (a NaN
+ * orientation window still fails the call), sift3d_amd_last_num_candidates is unaffected, and the result is a pure function of
+ * the unbudgeted list; what is saved is the describe of the deleted records (and whatever the caller does per keypoint
+ * afterwards), not the orientation step.  The selection runs on the device between orientation and the compaction, exact and
+ * deterministic, without a synchronisation of its own.
+ * Applies to SIFT3D_detect_keypoints, sift3d_amd_detect_keypoints_dev and sift3d_amd_detect_keypoints_typed, the verbatim pass of
+ * non-finite volumes included, until it is changed.  n < 0 fails and leaves the previous value.  copy_SIFT3D copies the budget;
+ * init_SIFT3D and a fresh struct have none.  The descriptor entry points, the dense path and the matcher do not look at it.
+ * With several GPUs (SIFT3D_NGPU > 1 / sift3d_amd_set_num_gpus) and a budget set a detect FAILS with a message that says so
+ * (the Z-slab ranks' gather carries no strengths); with no budget the multi-GPU path is unchanged. */
+int sift3d_amd_set_max_keypoints(SIFT3D *const sift3d, long n);
+long sift3d_amd_get_max_keypoints(const SIFT3D *const sift3d);
+/* out[i] = the strength of kp's record i, gathered on demand from the pyramid this struct holds in HBM (after a detect, with or
+ * without a budget; an unbudgeted detect pays nothing for it): out is a host array of kp->slab.num floats.  Fails with a message
+ * when the struct has no device pyramid, when a record lies outside its DoG level (or the store is empty: verify_keys), or when
+ * the pyramid is spread over several GPUs. */
+int sift3d_amd_keypoint_strengths(SIFT3D *const sift3d, const Keypoint_store *const kp, float *out);
+/* Profiling: HIP events (hipEvent_t) that the single-GPU detects of the calling thread record on their stream in front of the
+ * orientation step, behind it, and behind the budget's strength and selection kernels (which follow it directly; without a
+ * budget the last two coincide).  NULLs, the default, record nothing. */
+void sift3d_amd_set_orient_events(void *before_orient, void *after_orient, void *after_select);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

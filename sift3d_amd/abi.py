@@ -186,6 +186,34 @@ def set_mask(L: C.CDLL, sift3d, mask, shape=None) -> int:
     return L.sift3d_amd_set_mask(C.byref(sift3d), C.c_void_p(int(mask)), 1, nx, ny, nz)
 
 
+def set_max_keypoints(L: C.CDLL, sift3d, n: int) -> int:
+    """sift3d_amd_set_max_keypoints: the following detects on ``sift3d`` return the ``n`` strongest keypoints only (strength:
+    |DoG| of the keypoint's own voxel), in the reference's order; 0 = no budget.  Returns the C status (n < 0 fails and leaves
+    the previous value)."""
+    L.sift3d_amd_set_max_keypoints.argtypes = [C.POINTER(SIFT3D), C.c_long]
+    L.sift3d_amd_set_max_keypoints.restype = C.c_int
+    return L.sift3d_amd_set_max_keypoints(C.byref(sift3d), int(n))
+
+
+def get_max_keypoints(L: C.CDLL, sift3d) -> int:
+    L.sift3d_amd_get_max_keypoints.argtypes = [C.POINTER(SIFT3D)]
+    L.sift3d_amd_get_max_keypoints.restype = C.c_long
+    return int(L.sift3d_amd_get_max_keypoints(C.byref(sift3d)))
+
+
+def keypoint_strengths(L: C.CDLL, sift3d, kp) -> np.ndarray:
+    """sift3d_amd_keypoint_strengths: float32 [K], the strength of each record of ``kp`` from the pyramid ``sift3d`` holds on the
+    device after a detect.  Raises RuntimeError with the library's message on failure (no pyramid, a record outside its level,
+    an empty store, a pyramid spread over several GPUs)."""
+    L.sift3d_amd_keypoint_strengths.argtypes = [C.POINTER(SIFT3D), C.POINTER(Keypoint_store), C.POINTER(C.c_float)]
+    L.sift3d_amd_keypoint_strengths.restype = C.c_int
+    L.sift3d_amd_last_error.restype = C.c_char_p
+    out = np.zeros(int(kp.slab.num), np.float32)
+    if L.sift3d_amd_keypoint_strengths(C.byref(sift3d), C.byref(kp), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise RuntimeError((L.sift3d_amd_last_error() or b"").decode())
+    return out
+
+
 def volume_to_numpy(v: Volume) -> np.ndarray:
     """A copy of a ``Volume``'s elements as [nz, ny, nx] in their stored type."""
     dt = {code: d for d, code in TYPED_DTYPES.items()}[v.dtype]

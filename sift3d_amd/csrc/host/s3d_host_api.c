@@ -146,6 +146,12 @@ typedef struct {
     size_t mask_off[S3D_MAX_OCTAVES + 1];   /* first word of octave o; [mask_noct]: words in all */
     unsigned long long *d_mask_bits;
     unsigned long long *h_mask_bits;        /* host copy for the multi-GPU filter, fetched when first needed */
+    /* keypoint budget (sift3d_amd_set_max_keypoints): 0 none.  The candidates' strengths and the selection's scratch exist
+     * only while a budget is set, sized with the candidate list (ctx_ensure_candidates) */
+    long max_keypoints;
+    uint32_t sel_cap;
+    float *d_strength;
+    void *d_select;
 } s3d_ctx;
 
 /* words of c->d_red.  The input's maximum sits directly in front of the counters, so that the copy that fetches the
@@ -209,6 +215,8 @@ static void ctx_free_pyramid(s3d_ctx *c)
     dfree(&c->d_bits); dfree(&c->d_scratch);
     dfree(&c->d_cand_idx); dfree(&c->d_cand_tag); dfree(&c->d_keep); dfree(&c->d_kscratch);
     dfree(&c->d_R); dfree(&c->d_Rk); dfree(&c->d_xyzos); dfree(&c->d_sigma); dfree(&c->d_orient); dfree(&c->d_oritab);
+    dfree(&c->d_strength); dfree(&c->d_select);
+    c->sel_cap = 0;
     c->oritab_bytes = 0;
     c->nx = c->ny = c->nz = c->num_octaves = c->num_levels = 0;
     c->cand_cap = 0;
@@ -518,9 +526,21 @@ static int ctx_ensure_pyramid(SIFT3D *const sift3d, s3d_ctx *c)
     return SIFT3D_SUCCESS;
 }
 
+/* the strengths and the selection's scratch for `cap` candidates: only a struct with a budget pays for them */
+static int ctx_ensure_select(s3d_ctx *c, uint32_t cap)
+{
+    if (c->max_keypoints <= 0 || c->sel_cap >= cap) return SIFT3D_SUCCESS;
+    dfree(&c->d_strength); dfree(&c->d_select);
+    c->sel_cap = 0;
+    DEV(s3d_rt_malloc((void **)&c->d_strength, (size_t)cap * sizeof(float)));
+    DEV(s3d_rt_malloc(&c->d_select, s3d_k_select_scratch_bytes(cap)));
+    c->sel_cap = cap;
+    return SIFT3D_SUCCESS;
+}
+
 static int ctx_ensure_candidates(s3d_ctx *c, uint32_t cap)
 {
-    if (c->cand_cap >= cap) return SIFT3D_SUCCESS;
+    if (c->cand_cap >= cap) return ctx_ensure_select(c, c->cand_cap);
     dfree(&c->d_cand_idx); dfree(&c->d_cand_tag); dfree(&c->d_keep); dfree(&c->d_kscratch);
     dfree(&c->d_R); dfree(&c->d_Rk); dfree(&c->d_xyzos); dfree(&c->d_orient);
     c->cand_cap = 0;
@@ -533,7 +553,7 @@ static int ctx_ensure_candidates(s3d_ctx *c, uint32_t cap)
     DEV(s3d_rt_malloc((void **)&c->d_xyzos, (size_t)cap * 5 * sizeof(int32_t)));
     DEV(s3d_rt_malloc(&c->d_orient, s3d_k_orient_scratch_bytes(cap)));
     c->cand_cap = cap;
-    return SIFT3D_SUCCESS;
+    return ctx_ensure_select(c, cap);
 }
 
 static void fill_pyr_desc(const Pyramid *g, float *const *levels, s3d_pyramid_desc *pd)
@@ -902,6 +922,14 @@ static int build_gpyr_dev(SIFT3D *const sift3d, s3d_ctx *c, int with_extrema)
     return SIFT3D_SUCCESS;
 }
 
+/* profiling (scripts/keypoint_budget_cost.py): HIP events the calling thread's detects record on their stream in front of
+ * the orientation step, behind it, and behind the budget's selection; NULLs (the default) record nothing */
+static __thread void *g_orient_ev[3];
+void sift3d_amd_set_orient_events(void *before_orient, void *after_orient, void *after_select)
+{
+    g_orient_ev[0] = before_orient; g_orient_ev[1] = after_orient; g_orient_ev[2] = after_select;
+}
+
 /* detect_extrema (sift.c:1074-1212) + assign_orientations (sift.c:1264-1325) on the device */
 static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp)
 {
@@ -941,6 +969,7 @@ static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp
 
     fill_pyr_desc(g, c->d_level, &pd);
     {
+        if (g_orient_ev[0]) DEV(s3d_rt_event_record(g_orient_ev[0], c->stream));
         if (c->oritab_built && s3d_k_orient_wants_tab(&pd)) {
             /* tables and sigmas went out on the extrema stream beside the pyramid (build_gpyr_dev); that stream has been waited
              * for above */
@@ -957,6 +986,16 @@ static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp
                                  c->d_R, c->d_keep, NULL, c->d_orient, s3d_k_orient_wants_tab(&pd) ? c->d_oritab : NULL,
                                  c->d_count + 2, c->stream));
         }
+        if (g_orient_ev[1]) DEV(s3d_rt_event_record(g_orient_ev[1], c->stream));
+        if (c->max_keypoints > 0 && (unsigned long)c->max_keypoints < counts[0]) {
+            /* the budget: orientation has decided on every candidate; of those it kept, all but the max_keypoints strongest
+             * are cleared before the compaction, which then sees -- and the describe that follows pays for -- fewer records.
+             * (No more candidates than the budget: nothing can be cut, nothing is launched.) */
+            if (ctx_ensure_select(c, c->cand_cap)) return SIFT3D_FAILURE;
+            DEV(s3d_k_key_strength(&pd, c->d_cand_idx, c->d_cand_tag, c->d_keep, counts[0], c->d_strength, c->stream));
+            DEV(s3d_k_select_strongest(c->d_strength, c->d_keep, counts[0], (uint32_t)c->max_keypoints, c->d_select, c->stream));
+        }
+        if (g_orient_ev[2]) DEV(s3d_rt_event_record(g_orient_ev[2], c->stream));
         DEV(s3d_k_compact_keys(&pd, c->d_cand_idx, c->d_cand_tag, c->d_R, c->d_keep, counts[0], c->d_xyzos,
                                c->d_Rk, c->d_count + 1, c->d_kscratch, c->stream));
         DEV(s3d_rt_d2h(counts + 1, c->d_count + 1, 2 * sizeof(uint32_t), c->stream));
@@ -1121,6 +1160,36 @@ int sift3d_amd_have_mask(const SIFT3D *const sift3d)
     return c != NULL && c->mask_dims[0] != 0;
 }
 
+/* ---- keypoint budget (include/sift3d_amd.h) --------------------------------------------------------------------------------- */
+int sift3d_amd_set_max_keypoints(SIFT3D *const sift3d, long n)
+{
+    s3d_ctx *c;
+    if (sift3d == NULL) API_FAIL("sift3d_amd_set_max_keypoints: null argument");
+    if (n < 0) API_FAIL("sift3d_amd_set_max_keypoints: the budget must be 0 (none) or positive. Provided: %ld", n);
+    if ((c = sift_ctx(sift3d)) == NULL) {
+        if (n == 0) return SIFT3D_SUCCESS;                 /* a struct without a context has no budget */
+        if (!(sift3d->kernels.downsample_2 = ctx_new())) API_FAIL("sift3d_amd: out of device contexts");
+        c = sift_ctx(sift3d);
+    }
+    c->max_keypoints = n;
+    return SIFT3D_SUCCESS;
+}
+
+long sift3d_amd_get_max_keypoints(const SIFT3D *const sift3d)
+{
+    const s3d_ctx *c = sift3d ? sift_ctx(sift3d) : NULL;
+    return c ? c->max_keypoints : 0;
+}
+
+/* the Z-slab ranks' gather carries no strengths: a budget with several GPUs fails, it is not silently ignored */
+static int budget_check_single_gpu(const SIFT3D *sift3d)
+{
+    const s3d_ctx *c = sift_ctx(sift3d);
+    if (c == NULL || c->max_keypoints <= 0) return SIFT3D_SUCCESS;
+    API_FAIL("sift3d_amd: a keypoint budget (sift3d_amd_set_max_keypoints: %ld) is not supported with several GPUs; "
+             "clear it with 0 or detect on one GPU", c->max_keypoints);
+}
+
 /* a detect on a volume of other dimensions than the mask's fails: the mask is not silently ignored */
 static int mask_check_dims(const SIFT3D *sift3d, int nx, int ny, int nz)
 {
@@ -1184,7 +1253,7 @@ int SIFT3D_detect_keypoints(SIFT3D *const sift3d, const Image *const im, Keypoin
     }
     if (mgpu_for(sift3d) > 1) {                            /* Z-slabs over several GPUs (s3d_host_slab.c) */
         s3d_ctx *c = sift_ctx(sift3d);
-        if (mask_check_dims(sift3d, im->nx, im->ny, im->nz)) {
+        if (budget_check_single_gpu(sift3d) || mask_check_dims(sift3d, im->nx, im->ny, im->nz)) {
             free(dense);
             return SIFT3D_FAILURE;
         }
@@ -1540,6 +1609,58 @@ int sift3d_amd_describe_window_stats(SIFT3D *const sift3d, const Keypoint_store 
     return rc;
 }
 
+/* |D| of each record's own DoG voxel from the pyramid in HBM (include/sift3d_amd.h): the records go up as the candidate
+ * list's (index, tag) pairs and through the kernel the budget ranks by */
+int sift3d_amd_keypoint_strengths(SIFT3D *const sift3d, const Keypoint_store *const kp, float *out)
+{
+    const Pyramid *g;
+    s3d_ctx *c;
+    s3d_pyramid_desc pd;
+    uint32_t *h = NULL, *d_it = NULL;
+    float *d_out = NULL;
+    size_t num;
+    int rc = SIFT3D_FAILURE;
+    if (sift3d == NULL || kp == NULL || out == NULL) API_FAIL("sift3d_amd_keypoint_strengths: null argument");
+    g = &sift3d->gpyr;
+    c = sift_ctx(sift3d);
+    num = kp->slab.num;
+    if (!SIFT3D_have_gpyr(sift3d))
+        API_FAIL("sift3d_amd_keypoint_strengths: no device pyramid: run SIFT3D_detect_keypoints on this struct first");
+    if (c->pyramid_on_slabs)
+        API_FAIL("sift3d_amd_keypoint_strengths: the pyramid is spread over several GPUs; strengths need a single-GPU detect");
+    if (s3d_verify_keys(kp, sift3d->im.nx, sift3d->im.ny, sift3d->im.nz))
+        API_FAIL("sift3d_amd_keypoint_strengths: a keypoint lies outside the image, or there is none (verify_keys)");
+    if (num > 0xffffffffu) API_FAIL("sift3d_amd_keypoint_strengths: too many keypoints");
+    if ((h = (uint32_t *)malloc(num * 2 * sizeof(uint32_t))) == NULL) API_FAIL("sift3d_amd_keypoint_strengths: out of memory");
+    for (size_t i = 0; i < num; i++) {
+        const Keypoint *key = kp->buf + i;
+        const int oi = key->o - g->first_octave, ki = key->s - g->first_level;
+        const Image *lv = g->levels + (oi >= 0 && oi < g->num_octaves ? oi : 0) * g->num_levels;
+        const int x = (int)key->xd, y = (int)key->yd, z = (int)key->zd;
+        /* DoG level s lies between GSS levels s and s + 1, and the octave's own dimensions bound the voxel (verify_keys
+         * compares against the image's, which an odd dimension halves to less) */
+        if (oi < 0 || oi >= g->num_octaves || ki < 0 || ki + 1 >= g->num_levels || x < 0 || y < 0 || z < 0 || x >= lv->nx ||
+            y >= lv->ny || z >= lv->nz) {
+            free(h);
+            API_FAIL("sift3d_amd_keypoint_strengths: keypoint %zu (%d, %d, %d, o=%d, s=%d) lies outside its DoG level", i, x, y, z,
+                     key->o, key->s);
+        }
+        h[i] = (uint32_t)((size_t)x + (size_t)lv->nx * ((size_t)y + (size_t)lv->ny * (size_t)z));
+        h[num + i] = ((uint32_t)oi << 8) | (uint32_t)ki;
+    }
+    fill_pyr_desc(g, c->d_level, &pd);
+    if (s3d_rt_malloc((void **)&d_it, num * 2 * sizeof(uint32_t)) == 0 && s3d_rt_malloc((void **)&d_out, num * sizeof(float)) == 0 &&
+        s3d_rt_h2d(d_it, h, num * 2 * sizeof(uint32_t), c->stream) == 0 &&
+        s3d_k_key_strength(&pd, d_it, d_it + num, NULL, (uint32_t)num, d_out, c->stream) == 0 &&
+        s3d_rt_d2h(out, d_out, num * sizeof(float), c->stream) == 0 && s3d_rt_sync(c->stream) == 0)
+        rc = SIFT3D_SUCCESS;
+    if (d_it) s3d_rt_free(d_it);
+    if (d_out) s3d_rt_free(d_out);
+    free(h);
+    if (rc) API_FAIL("sift3d_amd_keypoint_strengths: %s", s3d_rt_last_error());
+    return SIFT3D_SUCCESS;
+}
+
 static void fill_desc_coords(const Keypoint_store *kp, SIFT3D_Descriptor *buf)
 {
     for (size_t i = 0; i < kp->slab.num; i++) {           /* sift.c:1920-1925 */
@@ -1666,6 +1787,7 @@ int copy_SIFT3D(const SIFT3D *const src, SIFT3D *const dst)
         memcpy(dc->mask_off, sc->mask_off, sizeof(dc->mask_off));
         dc->mask_noct = sc->mask_noct;
     }
+    if (sc != NULL && sc->max_keypoints > 0 && sift3d_amd_set_max_keypoints(dst, sc->max_keypoints)) return SIFT3D_FAILURE;
     if (sc == NULL || sc->d_im == NULL || src->im.nx <= 0 || sc->pyramid_on_slabs)
         return SIFT3D_SUCCESS;                            /* no image yet (a multi-GPU pyramid is not copied: parameters only) */
     {

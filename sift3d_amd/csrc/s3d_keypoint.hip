@@ -879,6 +879,184 @@ extern "C" int s3d_k_compact_keys(const s3d_pyramid_desc *pyr, const uint32_t *d
     return S3D_OK;
 }
 
+/* ---- keypoint budget: the strength of a candidate and the exact top-N selection ------------------------
+ * (extension: sift3d_amd_set_max_keypoints; OpenCV's nfeatures.)  The strength of candidate i is |D| of its own voxel,
+ * D the DoG voxel as build_dog stores it (sift.c:1052-1071): one f32 subtraction of the two GSS levels either side, the
+ * same two levels k_extrema_fused names L1 and L2 for keypoint level k = tag & 255 -- d_level[o * L + k] and [.. + k + 1].
+ * |a - b| == |b - a| bit for bit, so the operand order of im_subtract does not matter here.
+ *
+ * The selection is an MSB-first radix select over the bit patterns (a non-negative f32 orders like its uint32): four
+ * passes of 8 bits, each a histogram over the kept entries that still match the digits chosen so far -- wave-aggregated,
+ * then LDS, then one integer global atomic per non-empty bin and workgroup: order-free, hence bit-reproducible.  No
+ * kernel waits for another workgroup: every pass is its own launch, and a workgroup re-derives the digits chosen so far
+ * from the finished histograms of the earlier passes (sel_resolve: one wave, six shuffles per pass) instead of reading a
+ * state word some other kernel would have to write.  After the fourth pass the threshold T and the number of entries
+ * equal to T that still fit are known; an ordered count / scan / apply triple, the shape of k_ck_*, keeps the first of
+ * them in index order and clears every kept entry below T.  Fewer kept entries than the budget: pass 0's histogram
+ * says so and every later workgroup leaves at once. */
+#define SEL_HIST_WORDS (4 * 256)            /* the four passes' histograms */
+#define SEL_HEAD_WORDS (SEL_HIST_WORDS + 8) /* ... one word for k_ck_scan's total, padding; the block counters follow */
+
+__global__ void __launch_bounds__(256)
+k_key_strength(s3d_pyramid_desc pyr, const uint32_t *__restrict__ d_idx, const uint32_t *__restrict__ d_tag,
+               const uint32_t *__restrict__ d_keep, uint32_t num, float *__restrict__ d_strength)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= num || (d_keep != nullptr && d_keep[i] == 0u)) return;
+    const unsigned tag = d_tag[i], idx = d_idx[i];
+    const int lev = (int)(tag >> 8) * pyr.num_levels + (int)(tag & 255u);
+    d_strength[i] = fabsf(pyr.d_level[lev + 1][idx] - pyr.d_level[lev][idx]);
+}
+
+extern "C" int s3d_k_key_strength(const s3d_pyramid_desc *pyr, const uint32_t *d_idx, const uint32_t *d_tag,
+                                  const uint32_t *d_keep, uint32_t num, float *d_strength, s3d_stream stream)
+{
+    if (num == 0) return S3D_OK;
+    if (d_idx == nullptr || d_tag == nullptr) S3D_FAIL("a candidate list has indices and tags");
+    hipLaunchKernelGGL(k_key_strength, dim3(s3d_div_up(num, 256)), dim3(256), 0, (hipStream_t)stream, *pyr, d_idx, d_tag, d_keep,
+                       num, d_strength);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* What the finished histograms hist[0 .. npass) say: out[0] = the digits chosen so far (npass * 8 bits), out[1] = how many
+ * entries matching them are still to be kept (>= 1), out[2] = 0 iff no more entries are kept than `budget` (nothing to
+ * do).  Pass p's digit is the largest d with  #(digit > d) < k <= #(digit >= d)  among the entries matching the digits
+ * before it.  Wave 0 computes, lane l owning the digits 255 - 4l .. 252 - 4l; the caller's __syncthreads publishes. */
+__device__ __forceinline__ void sel_resolve(const uint32_t *__restrict__ hist, int npass, uint32_t budget, uint32_t *out)
+{
+    if (threadIdx.x >= 64u) return;
+    const unsigned lane = threadIdx.x;
+    uint32_t prefix = 0u, k = budget, active = 1u;
+    for (int p = 0; p < npass; p++) {
+        const uint32_t *h = hist + 256 * p + (252u - 4u * lane);
+        const uint32_t c[4] = {h[3], h[2], h[1], h[0]};                    /* descending digits */
+        const uint32_t sum = c[0] + c[1] + c[2] + c[3];
+        uint32_t incl = sum;
+        for (unsigned off = 1; off < 64; off <<= 1) {
+            const uint32_t v = __shfl_up(incl, off);
+            if (lane >= off) incl += v;
+        }
+        if (p == 0 && __shfl(incl, 63) <= budget) {                      /* wave-uniform */
+            active = 0u;
+            break;
+        }
+        const uint32_t excl = incl - sum;
+        const unsigned long long owner = __ballot(excl < k && k <= incl);   /* exactly one lane: 1 <= k <= total */
+        const int src = __popcll((owner & (0ull - owner)) - 1ull) & 63;
+        uint32_t r = k - excl, digit = 255u - 4u * lane;                    /* meaningful in lane src only */
+        for (int j = 0; j < 3 && r > c[j]; j++) {
+            r -= c[j];
+            digit--;
+        }
+        prefix = (prefix << 8) | __shfl(digit, src);
+        k = __shfl(r, src);
+    }
+    if (lane == 0) {
+        out[0] = prefix;
+        out[1] = k;
+        out[2] = active;
+    }
+}
+
+template <int PASS>
+__global__ void __launch_bounds__(256)
+k_sel_hist(const float *__restrict__ d_strength, const uint32_t *__restrict__ d_keep, uint32_t num, uint32_t budget,
+           uint32_t *hist /* earlier passes' bins are read, this pass's added to */)
+{
+    __shared__ uint32_t s_hist[256];
+    __shared__ uint32_t s_state[3];
+    const unsigned t = threadIdx.x, lane = t & 63u;
+    const size_t i = (size_t)blockIdx.x * 256u + t;
+    s_hist[t] = 0u;
+    sel_resolve(hist, PASS, budget, s_state);
+    __syncthreads();
+    if (PASS > 0 && s_state[2] == 0u) return;
+    const bool kept = i < num && d_keep[i] != 0u;
+    const uint32_t key = kept ? (__float_as_uint(d_strength[i]) & 0x7fffffffu) : 0u;
+    const bool in = kept && (PASS == 0 || (key >> ((32 - 8 * PASS) & 31)) == s_state[0]);
+    const uint32_t digit = (key >> (24 - 8 * PASS)) & 255u;
+    /* the leading digits are shared by most of a wave (strengths span a few binades): up to four of a wave's digits go in
+     * as one add each, what is left lane by lane */
+    unsigned long long todo = __ballot(in);
+    for (int it = 0; it < 4 && todo != 0ull; it++) {
+        const int lead = __popcll((todo & (0ull - todo)) - 1ull) & 63;
+        const uint32_t d = __shfl(digit, lead);
+        const unsigned long long same = __ballot(in && digit == d) & todo;
+        if ((int)lane == lead) atomicAdd(&s_hist[d], (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1ull) atomicAdd(&s_hist[digit], 1u);
+    __syncthreads();
+    if (s_hist[t] != 0u) atomicAdd(&hist[256 * PASS + t], s_hist[t]);
+}
+
+/* entries equal to the threshold, per workgroup (k_ck_scan turns the counts into offsets) */
+__global__ void __launch_bounds__(256)
+k_sel_tie_count(const float *__restrict__ d_strength, const uint32_t *__restrict__ d_keep, uint32_t num, uint32_t budget,
+                const uint32_t *__restrict__ hist, unsigned *__restrict__ block_count)
+{
+    __shared__ uint32_t s_state[3];
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    sel_resolve(hist, 4, budget, s_state);
+    __syncthreads();
+    const bool eq = s_state[2] != 0u && i < num && d_keep[i] != 0u &&
+                    (__float_as_uint(d_strength[i]) & 0x7fffffffu) == s_state[0];
+    unsigned total;
+    ck_block_scan(eq ? 1u : 0u, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+/* clears what lost: every kept entry below the threshold, and of those equal to it all but the first s_state[1] */
+__global__ void __launch_bounds__(256)
+k_sel_apply(const float *__restrict__ d_strength, uint32_t *__restrict__ d_keep, uint32_t num, uint32_t budget,
+            const uint32_t *__restrict__ hist, const unsigned *__restrict__ block_off)
+{
+    __shared__ uint32_t s_state[3];
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    sel_resolve(hist, 4, budget, s_state);
+    __syncthreads();
+    if (s_state[2] == 0u) return;
+    const bool kept = i < num && d_keep[i] != 0u;
+    const uint32_t key = kept ? (__float_as_uint(d_strength[i]) & 0x7fffffffu) : 0u;
+    const bool eq = kept && key == s_state[0];
+    unsigned total;
+    const unsigned incl = ck_block_scan(eq ? 1u : 0u, &total);
+    if (!kept) return;
+    if (key < s_state[0] || (eq && block_off[blockIdx.x] + incl - 1u >= s_state[1])) d_keep[i] = 0u;
+}
+
+extern "C" size_t s3d_k_select_scratch_bytes(uint32_t num)
+{
+    return ((size_t)SEL_HEAD_WORDS + (size_t)num / 256 + 2) * sizeof(uint32_t);
+}
+
+extern "C" int s3d_k_select_strongest(const float *d_strength, uint32_t *d_keep, uint32_t num, uint32_t budget,
+                                      void *d_scratch, s3d_stream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t *const hist = (uint32_t *)d_scratch, *const blocks = hist + SEL_HEAD_WORDS;
+    if (budget == 0) S3D_FAIL("a keypoint budget is positive");
+    if (num == 0 || budget >= num) return S3D_OK;          /* no more entries kept than the budget, whatever d_keep holds */
+    const unsigned nb = s3d_div_up(num, 256);
+    S3D_HIP(hipMemsetAsync(hist, 0, SEL_HIST_WORDS * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_sel_hist<0>, dim3(nb), dim3(256), 0, st, d_strength, d_keep, num, budget, hist);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sel_hist<1>, dim3(nb), dim3(256), 0, st, d_strength, d_keep, num, budget, hist);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sel_hist<2>, dim3(nb), dim3(256), 0, st, d_strength, d_keep, num, budget, hist);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sel_hist<3>, dim3(nb), dim3(256), 0, st, d_strength, d_keep, num, budget, hist);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sel_tie_count, dim3(nb), dim3(256), 0, st, d_strength, d_keep, num, budget, hist, blocks);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ck_scan, dim3(1), dim3(256), 0, st, blocks, nb, hist + SEL_HIST_WORDS);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sel_apply, dim3(nb), dim3(256), 0, st, d_strength, d_keep, num, budget, hist, blocks);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
 /* ---- descriptor ------------------------------------------------------------------------------------ */
 #define DESC_PER 4                         /* x-consecutive window voxels per chunk (one thread, one turn) */
 __device__ __forceinline__ void desc_bounds(float vc, float rad, float uf, int n, int *s, int *e)

@@ -86,6 +86,11 @@ class DeviceLib:
             L.s3d_k_compact_bits_multi_and.argtypes = [_vp, C.c_size_t, C.c_int, C.c_size_t, C.c_uint32, _vp, _vp, C.c_uint32,
                                                        C.c_uint32, _vp, _vp, _vp, _vp]
             L.s3d_k_mask_pack.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]
+        if hasattr(L, "s3d_k_select_strongest"):          # (absent from builds older than the keypoint budget)
+            L.s3d_k_key_strength.argtypes = [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]
+            L.s3d_k_select_scratch_bytes.argtypes = [C.c_uint32]
+            L.s3d_k_select_scratch_bytes.restype = C.c_size_t
+            L.s3d_k_select_strongest.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -180,6 +185,16 @@ class DeviceLib:
         self.check(self.L.s3d_k_compact_bits_multi_and(_vp(d_bits), nwords, nseg, seg_stride, idx_base, _vp(d_idx), _vp(d_tag),
                                                        tag, capacity, _vp(d_count), _vp(d_scratch), _vp(d_and), _vp(stream)),
                    "s3d_k_compact_bits_multi_and")
+
+    # --- keypoint budget ---------------------------------------------------------------------------------
+    def select_scratch_bytes(self, num: int) -> int:
+        return int(self.L.s3d_k_select_scratch_bytes(num))
+
+    def select_strongest(self, d_strength: int, d_keep: int, num: int, budget: int, d_scratch: int, stream=None) -> None:
+        """Clears d_keep[i] (uint32) of every kept entry that is not among the ``budget`` kept entries of largest d_strength
+        (float32, non-negative); ties go to the lower i (s3d_k_select_strongest)."""
+        self.check(self.L.s3d_k_select_strongest(_vp(d_strength), _vp(d_keep), num, budget, _vp(d_scratch), _vp(stream)),
+                   "s3d_k_select_strongest")
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
