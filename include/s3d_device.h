@@ -359,6 +359,14 @@ int s3d_k_describe(const s3d_pyramid_desc *pyr, const s3d_desc_key *d_keys, uint
  * described twice since the counters were last reset (reset != 0 clears them). */
 int s3d_k_describe_redo_stats(unsigned long long *described, unsigned long long *redone, int reset);
 
+/* Test aids of the descriptor kernel's back end (S3D_TESTING builds only).  A window voxel's 24 histogram contributions are
+ * f32 products while its scaled magnitude stays below 2^24 grid units and f64 fused multiply-adds otherwise; both give
+ * the same integers.  s3d_k_set_describe_f32_limit multiplies that limit by s in [0, 1] (0: every voxel takes the f64
+ * form); s3d_k_describe_path_stats reports how many voxels took each form since the last reset.  In the product library
+ * both fail: its kernel has neither the hook nor the counters. */
+int s3d_k_set_describe_f32_limit(float s);
+int s3d_k_describe_path_stats(unsigned long long *fast_vox, unsigned long long *slow_vox, int reset);
+
 /* Test / diagnostics aid: d_stats[2i] = number of voxels the descriptor window of keypoint i accepts, d_stats[2i+1] = a
  * checksum of their coordinates, produced by the descriptor kernel's own window enumeration. */
 int s3d_k_describe_window_stats(const s3d_pyramid_desc *pyr, const s3d_desc_key *d_keys, uint32_t num,

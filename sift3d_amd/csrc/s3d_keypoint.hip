@@ -18,6 +18,9 @@
  * contract is 1e-4) and normalised in f64 like the reference.
  */
 #include "s3d_math.h"
+#if defined(S3D_EMU)
+#include <cassert>
+#endif
 
 /* ---- icosahedron table (host) -- init_geometry, sift.c:215-326 ---------------------------------- */
 extern "C" void s3d_mesh_table(float *out)
@@ -1119,13 +1122,24 @@ __device__ __forceinline__ bool desc_window(const DescGeom &g, int x, int y, int
  *      barriers, table fills and normalisation run under the other's window.  (Rounds 2-3: one 1024-thread workgroup with
  *      16 copies of 64-bit fields, 15.6 ms; 32 copies of 32-bit fields: 14.3; this layout: 12.5 -- profiles/
  *      r04_describe_field32.txt.)
- *  (2) One VALU instruction per contribution.  A contribution (mag * bary_v) * (wx * wy * wz) is formed as
- *      fma(m_v, w_c, M) in f64 with M = 1.5 * 2^(52 - f): the product of two f32-derived doubles is exact, the single
- *      rounding of the fma lands on the fixed-point grid 2^-f, and the low 32 bits of the result's bit pattern ARE that
- *      fixed-point number modulo 2^32, so the low dword goes straight into ds_add_u32 and the fields are exact integer
- *      sums modulo 2^32: order free, bitwise reproducible, rounded to nearest.  The grid (f and a factor in [1, 2) on the
- *      magnitudes) is set per keypoint from its measured gradient mass, and the kernel proves after the window that no
- *      field wrapped -- see dw_scale in the kernel body.
+ *  (2) One plain f32 VALU instruction per contribution.  A contribution (mag * bary_v) * (wx * wy * wz) is one v_mul_f32
+ *      of two pre-scaled f32 operands, m_v' = m_v 2^(f - 74) (the power of two rides on fscale, which multiplies the
+ *      magnitude anyway) and w_c' = w_c 2^-75 (one extra multiply on the x weight pair), whose product lies in the
+ *      subnormal range of f32 or in its first normal binade: there the spacing is 2^-149 and the BIT PATTERN of the
+ *      correctly rounded product is the fixed-point integer round(m_v w_c 2^f), so it goes straight into ds_add_u32 and the
+ *      fields are exact integer sums modulo 2^32: order free, bitwise reproducible, rounded to nearest.  This holds up to
+ *      2^24 grid units per contribution and for operands >= +0 (a negative or negative-zero product would add 2^31), so a
+ *      voxel takes it only while its three vertex magnitudes are below 2^24 units (cell weights are <= 1) and have a clear
+ *      sign bit; every other voxel (an outlier above ~1/80 of its histogram copy's whole mass, an Inf or NaN, a sample
+ *      that resolve() left with a barycentric weight down to -1.2e-6) is flagged in its face index and takes the f64 form
+ *      after the chunk's fast voxels: fma((double)m_v', (double)w_c', 1.5 * 2^-97), whose low dword is the same integer
+ *      in two's complement modulo 2^32.  Both forms round the exact product of the SAME two f32 operands once onto the
+ *      same grid, so a descriptor does not depend on which form a voxel took (tests/test_describe_f32.py).
+ *      THE FAST FORM DEPENDS ON f32 SUBNORMALS BEING KEPT (float_denorm_mode_32 = 3, the compiler's default for gfx950;
+ *      the build passes no flush-to-zero flag and must not).  The grid (f and a factor in [1, 2) on the magnitudes) is
+ *      set per keypoint from its measured gradient mass, DW_GRID_K times coarser than the 32-bit fields could take (so
+ *      that all but outlier voxels stay below 2^24 units), and the kernel proves after the window that no field wrapped
+ *      -- see dw_scale in the kernel body.
  *  (3) The window weight expf(-sq / 2 sigma^2) comes from a per-keypoint table indexed by the integer squared distance
  *      when that is exact (integer centre, equal power-of-two units: every octave of a unit-voxel volume); the table
  *      entries are produced by the same restated glibc expf on the same float argument, so nothing changes bit-wise.
@@ -1145,6 +1159,14 @@ __device__ __forceinline__ bool desc_window(const DescGeom &g, int x, int y, int
 #define DW_WG_PER_CU 2                    /* resident workgroups per CU (their LDS must fit side by side) */
 #endif
 #define DW_NFIELD (2 * DW_NCOPY)           /* 32-bit histogram fields per bin: one per lane of a half wave */
+#ifndef DW_GRID_K
+#define DW_GRID_K 2                       /* the fields are filled to 1 / DW_GRID_K of their range (a power of two) */
+#endif
+#define DW_FSPLIT 74                      /* the contributions' scale 2^(f - 149) is split between the two factors of the f32 */
+#define DW_WSCALE 0x1p-75f                /* product so that both stay normal floats: 2^(f - DW_FSPLIT) on the magnitude, 2^-75 on the weight */
+#define DW_MFIX 0x1.8p-97                 /* 1.5 * 2^(52 - 149): the f64 form's fma addend on the same grid */
+#define DW_F32_UNITS 0x1p-50f             /* 2^24 grid units as a scaled magnitude: 2^(24 - DW_FSPLIT) */
+#define DW_SLOWF 32                       /* added to the face index of a live voxel that takes the f64 form (S3D_NFACES < 32) */
 #define DW_WAVES (DW_THREADS / 64)
 #define DW_HIST_WORDS (S3D_DESC_NUMEL * DW_NCOPY)
 #define DW_NOUT ((S3D_DESC_NUMEL + DW_THREADS - 1) / DW_THREADS)   /* histogram bins a thread finalises */
@@ -1308,6 +1330,42 @@ extern "C" int s3d_k_set_describe_lane_test(int on)
     S3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dw_lane_test), &on, sizeof(on)));
     return S3D_OK;
 }
+/* test aid: the factor on the magnitude up to which a voxel takes the f32 form of the back end (1: the product's limit of
+ * 2^24 grid units, 0: every voxel takes the f64 form) */
+__device__ float g_dw_f32_limit = 1.0f;
+extern "C" int s3d_k_set_describe_f32_limit(float s)
+{
+    if (!(s >= 0.0f && s <= 1.0f)) S3D_FAIL("f32 limit factor outside [0, 1]");
+    S3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dw_f32_limit), &s, sizeof(s)));
+    return S3D_OK;
+}
+/* test aid: live voxels that took [0] the f32 form, [1] the f64 form (redone windows count every time) */
+__device__ unsigned long long g_dw_path[2];
+extern "C" int s3d_k_describe_path_stats(unsigned long long *fast_vox, unsigned long long *slow_vox, int reset)
+{
+    unsigned long long h[2] = {0, 0};
+    S3D_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dw_path), sizeof(h)));
+    if (fast_vox) *fast_vox = h[0];
+    if (slow_vox) *slow_vox = h[1];
+    if (reset) {
+        const unsigned long long z[2] = {0, 0};
+        S3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_dw_path), z, sizeof(z)));
+    }
+    return S3D_OK;
+}
+#else
+/* the product library has neither the hook nor the counters (its kernel compares against a constant and counts nothing);
+ * the symbols that include/s3d_device.h declares exist and say so */
+extern "C" int s3d_k_set_describe_f32_limit(float s)
+{
+    (void)s;
+    S3D_FAIL("s3d_k_set_describe_f32_limit: testing builds only");
+}
+extern "C" int s3d_k_describe_path_stats(unsigned long long *fast_vox, unsigned long long *slow_vox, int reset)
+{
+    (void)fast_vox; (void)slow_vox; (void)reset;
+    S3D_FAIL("s3d_k_describe_path_stats: testing builds only");
+}
 #endif
 
 #define DW_WAVES_PER_EU (DW_WG_PER_CU * DW_THREADS / 256)          /* the CU's resident waves over its four SIMDs */
@@ -1410,8 +1468,7 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
     /* fixed-point grid of the histogram (see (2) above): 2^-f / fs, set from the window's measured gradient mass further
      * down (dw_scale) and proved sufficient after the fact */
     int fbits = 0;
-    float fscale = 1.0f;
-    double Mfix = 0.0;
+    float fscale = 1.0f;                                      /* fs 2^(fbits - DW_FSPLIT): what the magnitudes are multiplied with */
 
     const int tz = dw_opaque(tid);
     /* closed-form x-interval of row (y, z) in voxels, widened by 1e-3 (float error at 2048^3 is 2e-4) */
@@ -1466,8 +1523,12 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
      * voxels that the lanes of copy k worked on, and the bins' rounding noise relative to the descriptor's norm is
      * ~ sqrt(contributions per bin) * grid / |h|, with |h| ~ T / 20.  So: (1) T is estimated from one voxel at a
      * pseudo-random place in each of up to 512 rows spread over the window (loads issued here, consumed after the
-     * histogram has been cleared); (2) grid = 1.15 T_est / 32 * 1.35 / 2^32, i.e. ~1e-11 T -- the contract needs
-     * < 9e-11 T at three sigma for a bin of 4000 contributions; (3) every lane sums the mass it sends, and after the window
+     * histogram has been cleared); (2) grid = DW_GRID_K * 1.15 T_est / 16 * 1.35 / 2^32, i.e. ~5e-11 T with DW_GRID_K = 2:
+     * the factor buys the f32 form of the back end its range -- a voxel takes it while |w grad| < 2^24 grid units, ~1/83 of
+     * its copy's mass, i.e. ~45 times the mean voxel of a 60 000-voxel window (512^3 bench volume: 3.7e-6 of the voxels are
+     * above it) -- and costs rounding noise in proportion: worst |error| / (1e-4 |v| + 1e-7) on the emulator's volumes 0.06 /
+     * 0.14 / 0.26 / 0.42 / 0.81 for DW_GRID_K = 1 / 2 / 4 / 8 / 16 (tests/test_describe_f32.py asks for <= 0.25; the speed is
+     * the same from 2 to 16); (3) every lane sums the mass it sends, and after the window
      * the per-copy sums PROVE that no field wrapped (T_k / grid + rounding slack < 2^32 - 2^21; the 2^21 are kept for
      * fields whose sum is negative: barycentric weights down to -1.2e-6 are accepted, sift.c:50).  If the proof fails, or
      * the estimate was so far off that the grid came out more than 8x coarser than intended, the keypoint is redone with
@@ -1481,7 +1542,7 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
         floose = (int)DW_UNIFORM(31 - bexp - head);           /* frexp leaves bexp in a vector register: to a scalar one */
     }
     const double flimit = 4294967296.0 - 2097152.0;
-    const double fgoal = flimit / 1.35;
+    const double fgoal = flimit / 1.35 / (double)DW_GRID_K;
     auto set_scale = [&](double tk) {                         /* tk: the largest per-copy mass expected, unscaled */
         int f;
         float fs = 1.0f;
@@ -1492,15 +1553,14 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
             f = e - 1;
             fs = (float)(2.0 * mant);
             if (f > 100) { f = 100; fs = 1.0f; }
-            if (f < -60) { f = -60; fs = 1.0f; }
+            if (f < -50) { f = -50; fs = 1.0f; }               /* (fscale stays a normal float) */
         } else {
             /* no gradient seen: the grid that cannot wrap whatever the window holds (floose: level voxels are bounded by 1 --
              * scaled input, convex filters -- so a central difference is <= 1/u per axis); the proof then finds it coarse */
-            f = floose;
+            f = floose < -50 ? -50 : floose > 100 ? 100 : floose;
         }
         fbits = (int)DW_UNIFORM(f);                           /* scalar registers: they live across the whole window */
-        fscale = __uint_as_float(DW_UNIFORM(__float_as_uint(fs)));
-        Mfix = ldexp(1.5, 52 - fbits);
+        fscale = __uint_as_float(DW_UNIFORM(__float_as_uint(ldexpf(fs, f - DW_FSPLIT))));
     };
     /* (1) the sample of this thread: six neighbours of one accepted voxel */
     const int nsamp = COUNT_ONLY ? 0 : (nrows < DW_THREADS / 2 ? nrows : DW_THREADS / 2);
@@ -1554,7 +1614,8 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
                 w = s3d_expf_tab((float)((double)(-0.5f * (dx * dx + dy * dy + dz * dz)) * inv_sig2), sm.etab);
             }
             const float gx = 0.5f * (sp_xp - sp_xm) * iux, gy = 0.5f * (sp_yp - sp_ym) * iuy, gz = 0.5f * (sp_zp - sp_zm) * iuz;
-            est = w * DW_SQRT(gx * gx + gy * gy + gz * gz) * (float)sp_len;
+            const float sm_mag = w * DW_SQRT(gx * gx + gy * gy + gz * gz);
+            est = sm_mag * sm_mag < (float)S3D_BARY_EPS_D ? 0.0f : sm_mag * (float)sp_len;   /* (below the floor: sends nothing) */
         }
         est = dw_wave_sum_early(est, dw_opaque(lane));
         if (lane == 0) sm.est_part[tz >> 6] = est;
@@ -1588,9 +1649,16 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
     /* DW_ABL (scripts/build_file_variants.py, timing only, results are wrong): 1 = the histogram atomics are not issued (what the
      * VALU side costs alone), 2 = the front end stubbed to a few operations on the loaded values (what the LDS side costs alone),
      * 3 = plain LDS stores instead of the atomics (the queue without the read-modify-write), 4 = 1 and 2 together (row intervals,
-     * scans, look-ups, gathers and the back end's arithmetic), 5 = the back end not run at all (everything up to it) */
+     * scans, look-ups, gathers and the back end's arithmetic), 5 = the back end not run at all (everything up to it).  All five
+     * act on both forms of the back end (emit() below); under 2 and 4 no voxel is flagged for the f64 form. */
 #if defined(DW_ABL)
     unsigned abl_acc = 0u;
+#endif
+#if defined(S3D_TESTING)
+    const float f32lim = DW_F32_UNITS * g_dw_f32_limit;
+    unsigned npath_fast = 0u, npath_slow = 0u;
+#else
+    const float f32lim = DW_F32_UNITS;
 #endif
     auto front = [&](bool valid, float vbx, float vby, float vbz, float w, float gx, float gy, float gz) {
         DwVox v;
@@ -1628,14 +1696,15 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
         const int face = dw_face_fast(sm.mesh, sm.fcn, gr, &bary, &safe);
         const bool live = valid && !((double)gg < S3D_BARY_EPS_D);       /* icos_hist_bin's floor on |grad|^2, sift.c:1655 */
         const float mag = DW_SQRT(gg) * fscale;
-        mass = mass + (valid ? mag : 0.0f);                      /* (resolve() may move it by an ulp: the proof allows 1e-4) */
-#if defined(DW_BACK_FLAT)
-        v.face = live && gg <= 3.4028234664e38f ? face : -1;    /* (a non-finite magnitude times a zero weight would not be zero) */
-#else
-        v.face = live ? face : -1;
-#endif
+        /* only voxels that can send: one below the floor sends nothing, and where most of a window lies below it (a flat volume
+         * around an outlier) their mass made the grid up to 100 times coarser than the live voxels need.  A voxel whose floor
+         * test resolve() has yet to settle counts.  (resolve() may move mag by an ulp: the proof allows 1e-4) */
+        mass = mass + (valid && !(gg < 0.9998f * (float)S3D_BARY_EPS_D) ? mag : 0.0f);   /* (live, or floor_unsure: NaN counts) */
         v.safe = (safe && !floor_unsure) || !(live || (valid && floor_unsure));
         v.m0 = mag * bary.x; v.m1 = mag * bary.y; v.m2 = mag * bary.z;
+        /* a live voxel with a vertex magnitude of 2^24 grid units or more takes the f64 form (the largest of the three bounds every
+         * product, the cell weights being <= 1; Inf / NaN magnitudes make all three so, and the comparison false) */
+        v.face = live ? (fmaxf(fmaxf(v.m0, v.m1), v.m2) < f32lim ? face : face + DW_SLOWF) : -1;
         v.vbx = vbx; v.vby = vby; v.vbz = vbz;
 #if !defined(DW_NO_FMA)
         v.gx = gx; v.gy = gy; v.gz = gz;
@@ -1658,84 +1727,85 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
         v.face = s3d_icos_bin(sm.mesh, v3(rx, ry, rz), &bary);           /* -1 below the floor on |grad|^2 */
         const float mag = DW_SQRT(rx * rx + ry * ry + rz * rz) * fscale;
         v.m0 = mag * bary.x; v.m1 = mag * bary.y; v.m2 = mag * bary.z;
+        /* the search accepts barycentric weights down to -bary_eps: the f32 form only takes vertex magnitudes with a clear sign
+         * bit (-0 included) below 2^24 units */
+        const bool f32ok = v.m0 < f32lim && v.m1 < f32lim && v.m2 < f32lim &&
+                           ((__float_as_uint(v.m0) | __float_as_uint(v.m1) | __float_as_uint(v.m2)) >> 31) == 0u;
+        if (v.face >= 0 && !f32ok) v.face += DW_SLOWF;
     };
-    /* back: the trilinear spread over 8 cells x 3 vertices */
+    /* back: the trilinear spread over 8 cells x 3 vertices.  One field update: */
+    auto emit = [&](char *p, unsigned units) {
+#if defined(DW_ABL) && (DW_ABL == 1 || DW_ABL == 4)
+        abl_acc += units + (unsigned)(size_t)p;
+#elif defined(DW_ABL) && DW_ABL == 3
+        *reinterpret_cast<volatile unsigned *>(p) = units;
+#else
+        atomicAdd(reinterpret_cast<unsigned *>(p), units);
+#endif
+    };
+    /* f64form false: 24 f32 products whose bit patterns are the contributions (operands >= +0, below 2^24 units: see (2) in
+     * the kernel's header); true: the same operands through fma in f64, for the voxels flagged with DW_SLOWF */
+    auto spread = [&](const DwVox &v, const int face, const bool f64form) {
+        /* base cell and offsets inside it; the clamps only matter for the last-bit slack of the stepped coordinates.  dv in
+         * [+0, 1]: vb >= +0 and ib <= vb give dv >= +0, and the minimum keeps 1 - dv >= +0 when ib was clamped to 3 */
+        int ibx = (int)v.vbx, iby = (int)v.vby, ibz = (int)v.vbz;
+        ibx = ibx > 3 ? 3 : ibx; iby = iby > 3 ? 3 : iby; ibz = ibz > 3 ? 3 : ibz;
+        const float dvx = fminf(v.vbx - (float)ibx, 1.0f), dvy = fminf(v.vby - (float)iby, 1.0f), dvz = fminf(v.vbz - (float)ibz, 1.0f);
+        const unsigned cellb = (unsigned)(ibx + 4 * iby + 16 * ibz) * (unsigned)(S3D_NVERT * DW_NCOPY * 8) + copy8;
+        char *const p0 = hbase + cellb + (unsigned)sm.vofs[face];
+        char *const p1 = hbase + cellb + (unsigned)sm.vofs[S3D_NFACES + face];
+        char *const p2 = hbase + cellb + (unsigned)sm.vofs[2 * S3D_NFACES + face];
+        const float dxs = dvx * DW_WSCALE;                       /* (1 - dv) s = s - dv s exactly for a power of two s */
+        const float wxs[2] = {DW_WSCALE - dxs, dxs}, wys[2] = {1.0f - dvy, dvy}, wzs[2] = {1.0f - dvz, dvz};
+#pragma unroll
+        for (int ix = 0; ix < 2; ix++)
+#pragma unroll
+            for (int iy = 0; iy < 2; iy++) {
+                const float wxy = wxs[ix] * wys[iy];
+#pragma unroll
+                for (int iz = 0; iz < 2; iz++) {
+                    if (ibx + ix >= 4 || iby + iy >= 4 || ibz + iz >= 4) continue;        /* vb >= 0 holds */
+                    const float wc = wxy * wzs[iz];
+                    constexpr int DCB = S3D_NVERT * DW_NCOPY * 8;
+                    const int dc = (ix + 4 * iy + 16 * iz) * DCB;                          /* compile-time byte offset */
+                    if (!f64form) {
+                        const unsigned u0 = __float_as_uint(v.m0 * wc), u1 = __float_as_uint(v.m1 * wc), u2 = __float_as_uint(v.m2 * wc);
+#if defined(S3D_EMU)
+                        assert(u0 <= 0x01000000u && u1 <= 0x01000000u && u2 <= 0x01000000u);   /* (also: sign bit clear) */
+#endif
+                        emit(p0 + dc, u0); emit(p1 + dc, u1); emit(p2 + dc, u2);
+                    } else {
+                        const double wd = (double)wc;
+                        emit(p0 + dc, (unsigned)__double_as_longlong(fma((double)v.m0, wd, DW_MFIX)));
+                        emit(p1 + dc, (unsigned)__double_as_longlong(fma((double)v.m1, wd, DW_MFIX)));
+                        emit(p2 + dc, (unsigned)__double_as_longlong(fma((double)v.m2, wd, DW_MFIX)));
+                    }
+                }
+            }
+    };
     auto back = [&](const DwVox &v) {
 #if defined(DW_ABL) && DW_ABL == 5
         abl_acc += __float_as_uint(v.m0) + __float_as_uint(v.m1) + __float_as_uint(v.m2) + (unsigned)v.face + __float_as_uint(v.vbx + v.vby + v.vbz);
         return;
 #endif
-#if defined(DW_BACK_FLAT)
-        /* straight-line form: a dead voxel (face < 0) sends zeros through face 0's bins, a cell beyond the 4 x 4 x 4 grid gets the
-         * weight 0 -- fma(m, 0, Mfix) has a zero low dword, and adding 0 changes no LDS word wherever the static cell offset
-         * points -- so all 24 atomics are issued by every lane and no exec mask changes inside the voxel */
-        const bool dead = v.face < 0;
-        const int fc = dead ? 0 : v.face;
-        int ibx = (int)v.vbx, iby = (int)v.vby, ibz = (int)v.vbz;
-        ibx = ibx > 3 ? 3 : ibx; iby = iby > 3 ? 3 : iby; ibz = ibz > 3 ? 3 : ibz;
-        const float fx = v.vbx - (float)ibx, fy = v.vby - (float)iby, fz = v.vbz - (float)ibz;
-        const double dvx = (double)fx, dvy = (double)fy, dvz = (double)fz;
-        const double m0 = dead ? 0.0 : (double)v.m0, m1 = dead ? 0.0 : (double)v.m1, m2 = dead ? 0.0 : (double)v.m2;
-        const unsigned cellb = (unsigned)(ibx + 4 * iby + 16 * ibz) * (unsigned)(S3D_NVERT * DW_NCOPY * 8) + copy8;
-        char *const p0 = hbase + cellb + (unsigned)sm.vofs[fc];
-        char *const p1 = hbase + cellb + (unsigned)sm.vofs[S3D_NFACES + fc];
-        char *const p2 = hbase + cellb + (unsigned)sm.vofs[2 * S3D_NFACES + fc];
-        const double wxs[2] = {1.0 - dvx, ibx < 3 ? dvx : 0.0}, wys[2] = {1.0 - dvy, iby < 3 ? dvy : 0.0},
-                     wzs[2] = {1.0 - dvz, ibz < 3 ? dvz : 0.0};
-#pragma unroll
-        for (int ix = 0; ix < 2; ix++)
-#pragma unroll
-            for (int iy = 0; iy < 2; iy++) {
-                const double wxy = wxs[ix] * wys[iy];
-#pragma unroll
-                for (int iz = 0; iz < 2; iz++) {
-                    const double wc = wxy * wzs[iz];
-                    constexpr int DCB = S3D_NVERT * DW_NCOPY * 8;
-                    const int dc = (ix + 4 * iy + 16 * iz) * DCB;                          /* compile-time byte offset */
-                    atomicAdd(reinterpret_cast<unsigned *>(p0 + dc), (unsigned)__double_as_longlong(fma(m0, wc, Mfix)));
-                    atomicAdd(reinterpret_cast<unsigned *>(p1 + dc), (unsigned)__double_as_longlong(fma(m1, wc, Mfix)));
-                    atomicAdd(reinterpret_cast<unsigned *>(p2 + dc), (unsigned)__double_as_longlong(fma(m2, wc, Mfix)));
-                }
-            }
-#else
-        if (v.face < 0) return;
-        /* base cell and offsets inside it; the clamps only matter for the last-bit slack of the stepped coordinates */
-        int ibx = (int)v.vbx, iby = (int)v.vby, ibz = (int)v.vbz;
-        ibx = ibx > 3 ? 3 : ibx; iby = iby > 3 ? 3 : iby; ibz = ibz > 3 ? 3 : ibz;
-        const double dvx = (double)(v.vbx - (float)ibx), dvy = (double)(v.vby - (float)iby), dvz = (double)(v.vbz - (float)ibz);
-        const double m0 = (double)v.m0, m1 = (double)v.m1, m2 = (double)v.m2;
-        const unsigned cellb = (unsigned)(ibx + 4 * iby + 16 * ibz) * (unsigned)(S3D_NVERT * DW_NCOPY * 8) + copy8;
-        char *const p0 = hbase + cellb + (unsigned)sm.vofs[v.face];
-        char *const p1 = hbase + cellb + (unsigned)sm.vofs[S3D_NFACES + v.face];
-        char *const p2 = hbase + cellb + (unsigned)sm.vofs[2 * S3D_NFACES + v.face];
-        const double wxs[2] = {1.0 - dvx, dvx}, wys[2] = {1.0 - dvy, dvy}, wzs[2] = {1.0 - dvz, dvz};
-#pragma unroll
-        for (int ix = 0; ix < 2; ix++)
-#pragma unroll
-            for (int iy = 0; iy < 2; iy++) {
-                const double wxy = wxs[ix] * wys[iy];
-#pragma unroll
-                for (int iz = 0; iz < 2; iz++) {
-                    if (ibx + ix >= 4 || iby + iy >= 4 || ibz + iz >= 4) continue;        /* vb >= 0 holds */
-                    const double wc = wxy * wzs[iz];
-                    constexpr int DCB = S3D_NVERT * DW_NCOPY * 8;
-                    const int dc = (ix + 4 * iy + 16 * iz) * DCB;                          /* compile-time byte offset */
-#if defined(DW_ABL) && (DW_ABL == 1 || DW_ABL == 4)
-                    abl_acc += (unsigned)__double_as_longlong(fma(m0, wc, Mfix)) + (unsigned)(size_t)(p0 + dc);
-                    abl_acc += (unsigned)__double_as_longlong(fma(m1, wc, Mfix)) + (unsigned)(size_t)(p1 + dc);
-                    abl_acc += (unsigned)__double_as_longlong(fma(m2, wc, Mfix)) + (unsigned)(size_t)(p2 + dc);
-#elif defined(DW_ABL) && DW_ABL == 3
-                    *reinterpret_cast<volatile unsigned *>(p0 + dc) = (unsigned)__double_as_longlong(fma(m0, wc, Mfix));
-                    *reinterpret_cast<volatile unsigned *>(p1 + dc) = (unsigned)__double_as_longlong(fma(m1, wc, Mfix));
-                    *reinterpret_cast<volatile unsigned *>(p2 + dc) = (unsigned)__double_as_longlong(fma(m2, wc, Mfix));
-#else
-                    atomicAdd(reinterpret_cast<unsigned *>(p0 + dc), (unsigned)__double_as_longlong(fma(m0, wc, Mfix)));
-                    atomicAdd(reinterpret_cast<unsigned *>(p1 + dc), (unsigned)__double_as_longlong(fma(m1, wc, Mfix)));
-                    atomicAdd(reinterpret_cast<unsigned *>(p2 + dc), (unsigned)__double_as_longlong(fma(m2, wc, Mfix)));
+        if ((unsigned)v.face >= (unsigned)DW_SLOWF) return;    /* dead (-1), or left to back_slow() */
+        spread(v, v.face, false);
+    };
+    /* the chunk's voxels that need the f64 form, one after the other in ONE copy of the code (a loop that is not unrolled,
+     * entered only by waves that have such a lane): the common path pays a maximum and a branch for it */
+    auto back_slow = [&](const DwVox &v0, const DwVox &v1, const DwVox &v2, const DwVox &v3) {
+#if defined(DW_ABL) && DW_ABL == 5
+        return;
 #endif
-                }
-            }
-#endif
+        const int f01 = v0.face > v1.face ? v0.face : v1.face, f23 = v2.face > v3.face ? v2.face : v3.face;
+        if ((f01 > f23 ? f01 : f23) < DW_SLOWF) return;
+        /* (the four voxels move through one set of registers: selecting voxel j by index made the compiler park them in scratch) */
+        DwVox a = v0, b = v1, c = v2, d = v3;
+#pragma unroll 1
+        for (int j = 0; j < DESC_PER; j++) {
+            if (a.face >= DW_SLOWF) spread(a, a.face - DW_SLOWF, true);
+            a = b; b = c; c = d;
+        }
     };
     /* chunk c of the current round -> its first voxel and length */
     struct DwChunk { int x0, y, z, nval; unsigned fv; };
@@ -1868,7 +1938,17 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
                 c += cstep;
                 const bool more = c < total;
                 if (more) { ch = lookup(c); L = gather(ch); }
+#if defined(S3D_TESTING)
+                {
+                    const int fv[DESC_PER] = {v0.face, v1.face, v2.face, v3.face};
+                    for (int j = 0; j < DESC_PER; j++) {
+                        npath_fast += (unsigned)fv[j] < (unsigned)DW_SLOWF ? 1u : 0u;
+                        npath_slow += fv[j] >= DW_SLOWF ? 1u : 0u;
+                    }
+                }
+#endif
                 back(v0); back(v1); back(v2); back(v3);
+                back_slow(v0, v1, v2, v3);
                 if (!more) break;
             }
         }
@@ -1881,6 +1961,11 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
     if (abl_acc == 0x9e3779b9u) sm.win_chk = abl_acc;         /* (keeps the ablated arithmetic alive) */
 #endif
     if (tid == 0 && attempt == 0) atomicAdd(&g_dw_stat[0], 1ull);
+#if defined(S3D_TESTING)
+    if (npath_fast) atomicAdd(&g_dw_path[0], (unsigned long long)npath_fast);
+    if (npath_slow) atomicAdd(&g_dw_path[1], (unsigned long long)npath_slow);
+    npath_fast = npath_slow = 0u;
+#endif
     /* (3) the proof.  Copy k is fed by the 64 / DW_NFIELD lanes k, k + DW_NFIELD, ... of every wave: their masses together
      * bound what a field of the copy can hold; a contribution is rounded to the grid (<= 1/2 each, 24 per voxel, <= 4 turns
      * voxels per lane), a lane's float sum is short by < 1e-5 of itself.  The same sums tell whether an accepted voxel had a
@@ -1897,7 +1982,7 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
 #endif
         }
         if (lp < DW_NFIELD) {
-            double d = ldexp((double)mk, fbits) * 1.0001 + 48.0 * (double)turns * (double)(64 / DW_NFIELD);
+            double d = ldexp((double)mk, DW_FSPLIT) * 1.0001 + 48.0 * (double)turns * (double)(64 / DW_NFIELD);
             if (!(d < 1e18)) d = 1e18;
             if (mk != mk) sm.nan_seen = 1u;
             atomicAdd(&sm.copy_units[lp], (unsigned long long)d);
@@ -1914,7 +1999,7 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
      * normalise / clamp / normalise */
     double ss = 0.0;
     float v[DW_NOUT];
-    const double unscale = ldexp(1.0, -fbits) / (double)fscale;
+    const double unscale = ldexp(1.0, -DW_FSPLIT) / (double)fscale;   /* = 2^-fbits / fs */
 #pragma unroll
     for (int q = 0; q < DW_NOUT; q++) {
         const int b = tm + q * DW_THREADS;
@@ -1959,7 +2044,12 @@ k_describe_wg(s3d_pyramid_desc pyr, const s3d_desc_key *__restrict__ keys, uint3
         if (tid == 0 && attempt == 0) atomicAdd(&g_dw_stat[1], 1ull);
         double umax = 0.0;
         for (int k = 0; k < DW_NFIELD; k++) umax = fmax(umax, (double)sm.copy_units[k]);
-        const double tk = ldexp(umax, -fbits) / (double)fscale;
+        /* the bound of a copy is its mass plus the rounding slack of the proof, 48 * turns per lane group and wave: on a grid
+         * that came out far too coarse (a window whose samples all lay below the floor) the slack can be hundreds of times
+         * the mass, and a grid set from the bound would be that much too coarse again.  The mass alone sets the new grid;
+         * the new proof adds its own slack, which the 1.35 of fgoal has room for. */
+        umax = umax - 48.0 * (double)turns * (double)(64 / DW_NFIELD) * (double)DW_WAVES + (double)DW_WAVES;   /* (+: every wave's term was truncated) */
+        const double tk = umax > 0.0 ? ldexp(umax, -DW_FSPLIT) / (double)fscale : 0.0;
         __syncthreads();                                      /* every thread has read the bounds and the flags */
         set_scale(1.02 * tk);
         mass = 0.0f;
