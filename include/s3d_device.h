@@ -410,6 +410,15 @@ int s3d_k_dense_post(float *d_desc12, const float *d_in, size_t nvox, s3d_stream
 int s3d_k_inv_affine(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny, int dnz,
                      const double A[12], int interp, s3d_stream stream);
 
+/* ---- RANSAC consensus counts (s3d_resample.hip; the scoring loop of find_tform_ransac, imutil.c:4527-4552, 4802-4815) ----
+ * counts[m] = #{ i < npts : !(e(i,m) > thr2) },  e = |src_i - M_m [ref_i 1]^T|^2 in f64 with the host loop's operation order
+ * (x' = A0*x + A1*y + A2*z + A3 left to right, no contraction), so a NaN e counts and e == thr2 counts.  d_src, d_ref: npts x 3
+ * row major; d_models: nmodels x 12 (3 x 4 row major); d_counts: nmodels ints, zeroed by the call.  Integer atomics only: the
+ * counts do not depend on the schedule.  npts, nmodels >= 1; nmodels <= 65535 * S3D_RANSAC_TILE (the grid's y extent). */
+#define S3D_RANSAC_TILE 64               /* models a workgroup of 256 matches walks */
+int s3d_k_ransac_count(const double *d_src, const double *d_ref, uint32_t npts, const double *d_models, uint32_t nmodels,
+                       double thr2, int *d_counts, s3d_stream stream);
+
 /* ---- matcher (s3d_match.hip; replaces match_desc, sift.c:2892-2969) ------------------------------- */
 /* For each of the `na` query rows (row r = d_a + (d_a_sel ? d_a_sel[r] : r) * a_stride, 768 floats) the
  * smallest and second-smallest f64 sum of squared differences over the nb rows of d_b and the index of

@@ -527,6 +527,32 @@ int sift3d_amd_keypoint_strengths(SIFT3D *const sift3d, const Keypoint_store *co
  * budget the last two coincide).  NULLs, the default, record nothing. */
 void sift3d_amd_set_orient_events(void *before_orient, void *after_orient, void *after_select);
 
+/* ---- RANSAC: the hypotheses of find_tform_ransac scored on the device --------------------------------------------------------
+ * find_tform_ransac draws its num_iter four-point models exactly as before (the same rand() calls in the same order; scoring
+ * consumes none) and counts every model's inliers either in the host loop or in one kernel launch per batch of models
+ * (s3d_k_ransac_count).  A count is an integer computed with the same f64 operations either way, so both paths pick the same
+ * winner (the lowest iteration holding the maximum count) and return the same transform, bit for bit, and the same failures.
+ * The knob is process-wide (Ransac is 16 bytes by ABI and carries no field for it):
+ *   AUTO (default)  the device path when a device is usable and npts * num_iter is large enough to pay for the transfers
+ *                   (S3D_RANSAC_AUTO_MIN_WORK, s3d_host_reg.c); the host path otherwise, and silently, with the identical
+ *                   result, when no device is found or a device call fails;
+ *   HOST            always the host loop;
+ *   DEVICE          always the device; a missing device or a failing device call is SIFT3D_FAILURE with sift3d_amd_last_error set.
+ * Without a call to sift3d_amd_set_ransac_device the environment variable SIFT3D_RANSAC_DEVICE (-1 / 0 / 1) decides, read once
+ * per process (for LD_PRELOAD deployments of unchanged callers).  register_SIFT3D, register_SIFT3D_resample and regSift3D go
+ * through find_tform_ransac and need no change.  Device memory of a call (the matches, one batch of models and counts) is
+ * freed before it returns. */
+#define SIFT3D_AMD_RANSAC_AUTO (-1)
+#define SIFT3D_AMD_RANSAC_HOST 0
+#define SIFT3D_AMD_RANSAC_DEVICE 1
+int sift3d_amd_set_ransac_device(int mode);   /* other values: SIFT3D_FAILURE, the mode is left as it was */
+int sift3d_amd_get_ransac_device(void);
+int sift3d_amd_ransac_last_path(void);        /* 0 host, 1 device: the scoring path of the calling thread's last find_tform_ransac */
+/* Profiling: with on != 0 the device path brackets its transfers and kernels with HIP events, and
+ * sift3d_amd_ransac_last_device_ms returns their sum for the calling thread's last find_tform_ransac (0 on the host path). */
+void sift3d_amd_set_ransac_profile(int on);
+double sift3d_amd_ransac_last_device_ms(void);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

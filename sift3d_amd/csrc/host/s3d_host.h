@@ -25,6 +25,13 @@ void s3d_make_desc_key(const Keypoint *key, double xd, double yd, double zd, int
 /* fails (with a message) when a descriptor window is too wide for the kernel's row enumeration */
 int s3d_check_desc_windows(const s3d_desc_key *keys, size_t num, const s3d_pyramid_desc *pd);
 
+/* sets the calling thread's sift3d_amd_last_error text and prints it like every API failure (s3d_host_api.c) */
+void s3d_api_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+
+/* find_tform_ransac draws and scores its models in batches of this many (12 doubles and one count each): what the host
+ * and the device hold for them does not grow with num_iter */
+#define S3D_RANSAC_BATCH 4096
+
 /* ---- one process, N GPUs behind the reference entry points (s3d_host_slab.c) --------------------------- */
 struct s3d_mgpu;
 int s3d_mgpu_wanted(const struct s3d_mgpu *m);            /* > 1: the multi-GPU path is switched on */

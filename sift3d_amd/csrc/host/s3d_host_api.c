@@ -17,6 +17,7 @@
 #include <float.h>
 #include <math.h>
 #include <pthread.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -62,6 +63,15 @@ static __thread char g_api_err[512];
     } while (0)
 
 const char *sift3d_amd_last_error(void) { return g_api_err; }
+
+void s3d_api_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_api_err, sizeof(g_api_err), fmt, ap);
+    va_end(ap);
+    S3D_MSG("%s\n", g_api_err);
+}
 
 /* ---- device context registry ------------------------------------------------------------------------ */
 #define S3D_DESC_BATCHES 4

@@ -11,7 +11,8 @@
  *   im_inv_transform / im_resample            imutil.c:2040-2244 -- the warp itself runs on the device
  *   Reg_SIFT3D                                reg/reg.c:121-441
  *
- * Host C; the device does detection, description, matching (SIFT3D_nn_match) and the resampling.
+ * Host C; the device does detection, description, matching (SIFT3D_nn_match), the resampling and, where it pays, the
+ * scoring of the RANSAC hypotheses (s3d_k_ransac_count).
  */
 #include <float.h>
 #include <math.h>
@@ -345,21 +346,148 @@ static int s3d_solve_affine(const double *src, const double *ref, int npts, int 
 
 /* ---- RANSAC --------------------------------------------------------------------------------------- */
 /* k distinct integers of 0..n-1 by a partial Fisher-Yates shuffle on libc rand(), call for call the
- * reference's n_choose_k: same seed, same glibc => same samples. */
+ * reference's n_choose_k: same seed, same glibc => same samples.  scratch holds the identity on entry and again on
+ * return: the reference refills it on every draw, here the k swaps are undone instead (an n-long fill per draw is the
+ * largest host term once the scoring runs on the device); the picks are the same. */
 static int s3d_n_choose_k(int n, int k, int *out /* k */, int *scratch /* n */)
 {
-    if (n < k || k < 1) return SIFT3D_FAILURE;
-    for (int i = 0; i < n; i++) scratch[i] = i;
+    int js[8];
+    if (n < k || k < 1 || k > 8) return SIFT3D_FAILURE;
     for (int i = 0; i < k; i++) {
         const int j = i + rand() % (n - i);
         const int t = scratch[i]; scratch[i] = scratch[j]; scratch[j] = t;
+        js[i] = j;
     }
     memcpy(out, scratch, sizeof(int) * k);
+    for (int i = k - 1; i >= 0; i--) {
+        const int t = scratch[i]; scratch[i] = scratch[js[i]]; scratch[js[i]] = t;
+    }
     return SIFT3D_SUCCESS;
 }
 
+/* -- where the hypotheses are scored (sift3d_amd.h: sift3d_amd_set_ransac_device) -- */
+/* AUTO scores on the device from this many affine applications (npts * num_iter) on.  profiles/ransac_cost.txt, part 2, has
+ * the measured grid this is taken from: the smallest product at which the device form beat the host form by more than the
+ * host form's own min-max spread was 200 x 500 = 100 000 (0.236 against 0.304 ms), rounded up to a power of two.  Below it
+ * (60 x 500) one allocation, upload, launch and download cost more than the host loop. */
+#define S3D_RANSAC_AUTO_MIN_WORK (1L << 17)
+
+#define S3D_RANSAC_MODE_UNSET (-2)
+static int g_ransac_mode = S3D_RANSAC_MODE_UNSET;      /* process-wide */
+static int g_ransac_profile;
+static __thread int g_ransac_last_path;
+static __thread double g_ransac_last_ms;
+
+static int s3d_ransac_mode_ok(long m) { return m == SIFT3D_AMD_RANSAC_AUTO || m == SIFT3D_AMD_RANSAC_HOST || m == SIFT3D_AMD_RANSAC_DEVICE; }
+
+int sift3d_amd_get_ransac_device(void)
+{
+    int m = __atomic_load_n(&g_ransac_mode, __ATOMIC_RELAXED);
+    if (m == S3D_RANSAC_MODE_UNSET) {                      /* no call yet: SIFT3D_RANSAC_DEVICE of the environment, read once */
+        const char *e = getenv("SIFT3D_RANSAC_DEVICE");
+        char *end = NULL;
+        const long v = e != NULL && *e ? strtol(e, &end, 10) : SIFT3D_AMD_RANSAC_AUTO;
+        m = (end == NULL || *end == '\0') && s3d_ransac_mode_ok(v) ? (int)v : SIFT3D_AMD_RANSAC_AUTO;
+        int unset = S3D_RANSAC_MODE_UNSET;
+        if (!__atomic_compare_exchange_n(&g_ransac_mode, &unset, m, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) m = unset;
+    }
+    return m;
+}
+
+int sift3d_amd_set_ransac_device(int mode)
+{
+    if (!s3d_ransac_mode_ok(mode)) {
+        s3d_api_set_error("sift3d_amd_set_ransac_device: the mode must be -1 (auto), 0 (host) or 1 (device). Provided: %d", mode);
+        return SIFT3D_FAILURE;
+    }
+    __atomic_store_n(&g_ransac_mode, mode, __ATOMIC_RELAXED);
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_ransac_last_path(void) { return g_ransac_last_path; }
+void sift3d_amd_set_ransac_profile(int on) { __atomic_store_n(&g_ransac_profile, on != 0, __ATOMIC_RELAXED); }
+double sift3d_amd_ransac_last_device_ms(void) { return g_ransac_last_ms; }
+
+/* the consensus set of one model: tform_err_sq (imutil.c:4527-4552) over every match, s3d_apply_Affine_xyz's operation
+ * order.  Returns its length; the members go to cset unless that is NULL.  (s3d_k_ransac_count computes the same length.) */
+static int s3d_ransac_consensus(const double *src, const double *ref, int npts, const double *A, double thr2, int *cset)
+{
+    int len = 0;
+    for (int i = 0; i < npts; i++) {
+        const double *r = ref + (size_t)i * IM_NDIMS, *s = src + (size_t)i * IM_NDIMS;
+        const double xo = A[0] * r[0] + A[1] * r[1] + A[2] * r[2] + A[3];
+        const double yo = A[4] * r[0] + A[5] * r[1] + A[6] * r[2] + A[7];
+        const double zo = A[8] * r[0] + A[9] * r[1] + A[10] * r[2] + A[11];
+        const double e = (s[0] - xo) * (s[0] - xo) + (s[1] - yo) * (s[1] - yo) + (s[2] - zo) * (s[2] - zo);
+        if (e > thr2) continue;
+        if (cset != NULL) cset[len] = i;
+        len++;
+    }
+    return len;
+}
+
+/* the device side of one find_tform_ransac call: one allocation holding the matches, a batch of models and their counts */
+typedef struct {
+    void *d_buf, *ev0, *ev1;
+    double *d_src, *d_ref, *d_models;
+    int *d_counts;
+    double ms;
+} s3d_ransac_dev;
+
+static void s3d_ransac_dev_close(s3d_ransac_dev *d)
+{
+    if (d->ev0) s3d_rt_event_destroy(d->ev0);
+    if (d->ev1) s3d_rt_event_destroy(d->ev1);
+    s3d_rt_free(d->d_buf);
+    memset(d, 0, sizeof(*d));
+}
+
+static int s3d_ransac_dev_lap(s3d_ransac_dev *d)          /* adds ev0 -> ev1 to the call's device time */
+{
+    float ms = 0.0f;
+    if (d->ev0 == NULL) return 0;
+    if (s3d_rt_event_elapsed_ms(d->ev0, d->ev1, &ms)) return -1;
+    d->ms += ms;
+    return 0;
+}
+
+static int s3d_ransac_dev_open(s3d_ransac_dev *d, const double *src, const double *ref, int npts)
+{
+    const size_t pts = sizeof(double) * IM_NDIMS * (size_t)npts, mod = sizeof(double) * 12 * S3D_RANSAC_BATCH;
+    memset(d, 0, sizeof(*d));
+    if (s3d_rt_malloc(&d->d_buf, 2 * pts + mod + sizeof(int) * S3D_RANSAC_BATCH)) return -1;
+    d->d_src = (double *)d->d_buf;
+    d->d_ref = (double *)((char *)d->d_buf + pts);
+    d->d_models = (double *)((char *)d->d_buf + 2 * pts);
+    d->d_counts = (int *)((char *)d->d_buf + 2 * pts + mod);
+    if (__atomic_load_n(&g_ransac_profile, __ATOMIC_RELAXED) &&
+        (s3d_rt_event_create(&d->ev0) || s3d_rt_event_create(&d->ev1) || s3d_rt_event_record(d->ev0, NULL)))
+        return -1;
+    if (s3d_rt_h2d(d->d_src, src, pts, NULL) || s3d_rt_h2d(d->d_ref, ref, pts, NULL)) return -1;
+    if (d->ev1 && s3d_rt_event_record(d->ev1, NULL)) return -1;
+    return s3d_ransac_dev_lap(d);
+}
+
+static int s3d_ransac_dev_score(s3d_ransac_dev *d, const double *models, int nb, int npts, double thr2, int *counts)
+{
+    if (d->ev0 && s3d_rt_event_record(d->ev0, NULL)) return -1;
+    if (s3d_rt_h2d(d->d_models, models, sizeof(double) * 12 * (size_t)nb, NULL) ||
+        s3d_k_ransac_count(d->d_src, d->d_ref, (uint32_t)npts, d->d_models, (uint32_t)nb, thr2, d->d_counts, NULL) ||
+        s3d_rt_d2h(counts, d->d_counts, sizeof(int) * (size_t)nb, NULL))
+        return -1;
+    if (d->ev1 && s3d_rt_event_record(d->ev1, NULL)) return -1;
+    if (s3d_rt_sync(NULL)) return -1;
+    return s3d_ransac_dev_lap(d);
+}
+
+/* Three phases per batch of at most S3D_RANSAC_BATCH iterations: draw the batch's models (today's loop head: the same rand()
+ * calls in the same order -- scoring consumes none), score them (host loop or s3d_k_ransac_count: the same integers), and keep
+ * the first model holding the largest count so far (`>` is strict, as the reference's len > len_best).  The winner's consensus
+ * set is then recomputed on the host for that single model, and the tail is the reference's. */
 int find_tform_ransac(const Ransac *const ran, const Mat_rm *const src, const Mat_rm *const ref, void *const tform)
 {
+    g_ransac_last_path = 0;
+    g_ransac_last_ms = 0.0;
     if (tform_get_type(tform) != AFFINE) {
         puts("find_tform_ransac: unsupported transformation type \n");
         return SIFT3D_FAILURE;
@@ -378,47 +506,90 @@ int find_tform_ransac(const Ransac *const ran, const Mat_rm *const src, const Ma
         printf("Not enough matched points \n");
         return SIFT3D_FAILURE;
     }
+    const double *const S = src->u.data_double, *const R = ref->u.data_double;
+    const double thr2 = ran->err_thresh * ran->err_thresh;
+    /* the scoring path */
+    const int mode = sift3d_amd_get_ransac_device();
+    int on_dev = 0, ndev = 0;
+    if (mode == SIFT3D_AMD_RANSAC_DEVICE ||
+        (mode == SIFT3D_AMD_RANSAC_AUTO && (double)npts * (double)ran->num_iter >= (double)S3D_RANSAC_AUTO_MIN_WORK)) {
+        on_dev = s3d_rt_device_count(&ndev) == 0 && ndev > 0;
+        if (!on_dev && mode == SIFT3D_AMD_RANSAC_DEVICE) {
+            s3d_api_set_error("find_tform_ransac: scoring on the device was asked for (SIFT3D_AMD_RANSAC_DEVICE) but no device "
+                              "is usable (%d found): %s", ndev, s3d_rt_last_error());
+            return SIFT3D_FAILURE;
+        }
+    }
     int rc = SIFT3D_FAILURE, len_best = 0;
     Affine cur;
-    int *cset = (int *)malloc(sizeof(int) * npts), *best = (int *)malloc(sizeof(int) * npts);
-    int *scratch = (int *)malloc(sizeof(int) * npts);
-    double *ps = NULL, *pr = NULL;
+    s3d_ransac_dev dev;
+    memset(&dev, 0, sizeof(dev));
+    int *best = (int *)malloc(sizeof(int) * npts), *scratch = (int *)malloc(sizeof(int) * npts);
+    int *counts = (int *)malloc(sizeof(int) * S3D_RANSAC_BATCH);
+    double *models = (double *)malloc(sizeof(double) * 12 * S3D_RANSAC_BATCH);
+    double *ps = NULL, *pr = NULL, best_model[12];
     if (init_Affine(&cur, dim)) {
-        free(cset); free(best); free(scratch);
+        free(best); free(scratch); free(counts); free(models);
         return SIFT3D_FAILURE;
     }
-    if (!cset || !best || !scratch) goto done;
-    const double thr2 = ran->err_thresh * ran->err_thresh;
-    for (int it = 0; it < ran->num_iter; it++) {
-        int pick[8], ret;
-        double s4[8 * IM_NDIMS], r4[8 * IM_NDIMS];
-        do {                                               /* singular samples are redrawn (imutil.c:4797-4800) */
-            if (s3d_n_choose_k(npts, nterms, pick, scratch)) goto done;
-            for (int i = 0; i < nterms; i++)
-                for (int j = 0; j < dim; j++) {
-                    s4[i * dim + j] = src->u.data_double[(size_t)pick[i] * dim + j];
-                    r4[i * dim + j] = ref->u.data_double[(size_t)pick[i] * dim + j];
-                }
-            ret = s3d_solve_affine(s4, r4, nterms, dim, &cur);
-        } while (ret == SIFT3D_SINGULAR);
-        if (ret != SIFT3D_SUCCESS) goto done;
-        int len = 0;
-        for (int i = 0; i < npts; i++) {                   /* tform_err_sq, imutil.c:4527-4552 */
-            double xo, yo, zo;
-            const double *r = ref->u.data_double + (size_t)i * dim, *s = src->u.data_double + (size_t)i * dim;
-            s3d_apply_Affine_xyz(&cur, r[0], r[1], r[2], &xo, &yo, &zo);
-            const double e = (s[0] - xo) * (s[0] - xo) + (s[1] - yo) * (s[1] - yo) + (s[2] - zo) * (s[2] - zo);
-            if (e > thr2) continue;
-            cset[len++] = i;
+    if (!best || !scratch || !counts || !models) goto done;
+    for (int i = 0; i < npts; i++) scratch[i] = i;
+    if (on_dev && s3d_ransac_dev_open(&dev, S, R, npts)) {
+        s3d_ransac_dev_close(&dev);
+        if (mode == SIFT3D_AMD_RANSAC_DEVICE) goto dev_failed;
+        on_dev = 0;                                        /* AUTO: the host loop gives the identical result */
+    }
+    g_ransac_last_path = on_dev;
+    for (int it0 = 0; it0 < ran->num_iter; it0 += S3D_RANSAC_BATCH) {
+        int nb = ran->num_iter - it0 < S3D_RANSAC_BATCH ? ran->num_iter - it0 : S3D_RANSAC_BATCH, draw_failed = 0, improved = 0;
+        for (int b = 0; b < nb; b++) {                     /* draw */
+            int pick[8], ret;
+            double s4[8 * IM_NDIMS], r4[8 * IM_NDIMS];
+            do {                                           /* singular samples are redrawn (imutil.c:4797-4800) */
+                if ((ret = s3d_n_choose_k(npts, nterms, pick, scratch)) != SIFT3D_SUCCESS) break;
+                for (int i = 0; i < nterms; i++)
+                    for (int j = 0; j < dim; j++) {
+                        s4[i * dim + j] = S[(size_t)pick[i] * dim + j];
+                        r4[i * dim + j] = R[(size_t)pick[i] * dim + j];
+                    }
+                ret = s3d_solve_affine(s4, r4, nterms, dim, &cur);
+            } while (ret == SIFT3D_SINGULAR);
+            if (ret != SIFT3D_SUCCESS) {                   /* a hard error: the iterations before this one still count, as */
+                nb = b;                                    /* in the one-by-one loop, which had scored them by now */
+                draw_failed = 1;
+                break;
+            }
+            memcpy(models + (size_t)b * 12, cur.A.u.data_double, sizeof(double) * 12);
         }
-        if (len > len_best) {
-            len_best = len;
-            memcpy(best, cset, sizeof(int) * len);
+        if (on_dev && nb > 0 && s3d_ransac_dev_score(&dev, models, nb, npts, thr2, counts)) {   /* score */
+            s3d_ransac_dev_close(&dev);
+            if (mode == SIFT3D_AMD_RANSAC_DEVICE) goto dev_failed;
+            on_dev = g_ransac_last_path = 0;               /* AUTO: this batch and the rest on the host */
+        }
+        if (!on_dev)
+            for (int b = 0; b < nb; b++) counts[b] = s3d_ransac_consensus(S, R, npts, models + (size_t)b * 12, thr2, NULL);
+        for (int b = 0; b < nb; b++)                       /* select */
+            if (counts[b] > len_best) {
+                len_best = counts[b];
+                memcpy(best_model, models + (size_t)b * 12, sizeof(best_model));
+                improved = 1;
+            }
+        g_ransac_last_ms = dev.ms;
+        if (improved) {                                    /* the best sample's model so far is left in tform, whatever follows */
+            if (cur.A.u.data_double == NULL || cur.A.num_rows != dim || cur.A.num_cols != nterms) goto done;
+            memcpy(cur.A.u.data_double, best_model, sizeof(best_model));
             if (copy_tform(&cur, tform)) goto done;
         }
+        if (draw_failed) goto done;
     }
     if (len_best < 5) {                                    /* min_num_inliers, imutil.c:4783 */
         puts("find_tform_ransac: No good model was found! \n");
+        goto done;
+    }
+    if (s3d_ransac_consensus(S, R, npts, best_model, thr2, best) != len_best) {
+        /* the two scoring paths compute the same integers: this is a defect (of the device's counts), not an input's property */
+        s3d_api_set_error("find_tform_ransac: the winner's consensus set, recomputed on the host, does not have the %d members it "
+                          "was scored with (%s path)", len_best, g_ransac_last_path ? "device" : "host");
         goto done;
     }
     /* least-squares refinement on the consensus set (SIFT3D_RANSAC_REFINE, imutil.c:4840-4856) */
@@ -427,8 +598,8 @@ int find_tform_ransac(const Ransac *const ran, const Mat_rm *const src, const Ma
     if (!ps || !pr) goto done;
     for (int i = 0; i < len_best; i++)
         for (int j = 0; j < dim; j++) {
-            ps[(size_t)i * dim + j] = src->u.data_double[(size_t)best[i] * dim + j];
-            pr[(size_t)i * dim + j] = ref->u.data_double[(size_t)best[i] * dim + j];
+            ps[(size_t)i * dim + j] = S[(size_t)best[i] * dim + j];
+            pr[(size_t)i * dim + j] = R[(size_t)best[i] * dim + j];
         }
     switch (s3d_solve_affine(ps, pr, len_best, dim, &cur)) {
     case SIFT3D_SUCCESS:
@@ -438,8 +609,12 @@ int find_tform_ransac(const Ransac *const ran, const Mat_rm *const src, const Ma
     default: goto done;
     }
     rc = SIFT3D_SUCCESS;
+    goto done;
+dev_failed:
+    s3d_api_set_error("find_tform_ransac: scoring on the device (SIFT3D_AMD_RANSAC_DEVICE) failed: %s", s3d_rt_last_error());
 done:
-    free(cset); free(best); free(scratch); free(ps); free(pr);
+    s3d_ransac_dev_close(&dev);
+    free(best); free(scratch); free(counts); free(models); free(ps); free(pr);
     cleanup_tform(&cur);
     return rc;
 }

@@ -1,5 +1,5 @@
-/* s3d_resample.hip -- inverse affine warp of a volume (the one data-parallel piece of the
- * registration tail).
+/* s3d_resample.hip -- the device unit of the registration tail: the inverse affine warp of a
+ * volume and, at the end of the file, the consensus counts of find_tform_ransac's hypotheses.
  *
  * im_inv_transform (imutil/imutil.c:2040-2085): every output voxel (x, y, z) is pushed through the
  * transform, (tx, ty, tz) = A [x y z 1]^T in f64 (apply_Affine_xyz, imutil.c:2651-2672), and the source
@@ -95,6 +95,60 @@ extern "C" int s3d_k_inv_affine(const float *d_src, int snx, int sny, int snz, i
                            dny, dnz, a);
     else
         S3D_FAIL("unrecognized interpolation type");
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* ---- RANSAC consensus counts (find_tform_ransac's scoring loop, imutil.c:4527-4552 + 4802-4815) ---------------------------
+ * counts[m] = #{ i : !(e(i, m) > thr2) }, e the squared residual of match i under model m in f64, with the host loop's
+ * operation order and no contraction, so a count is the integer the host loop finds.  One thread keeps one match (six doubles
+ * in registers) and walks the S3D_RANSAC_TILE models of its workgroup; a model's address is wave-uniform, so its twelve
+ * doubles arrive through the scalar cache and cost no vector or LDS bandwidth.  Per model one __ballot + popcount per wave,
+ * the four waves' partial sums in LDS, and at the end one integer atomicAdd per model per workgroup: integer sums do not
+ * depend on the order, so the counts are exact whatever the schedule.  No thread leaves early (the ballots are collective). */
+__global__ void __launch_bounds__(256)
+k_ransac_count(const double *__restrict__ src, const double *__restrict__ ref, uint32_t npts, const double *__restrict__ models,
+               uint32_t nmodels, double thr2, int *__restrict__ counts)
+{
+    __shared__ int s_part[4][S3D_RANSAC_TILE];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t i = blockIdx.x * 256u + tid;
+    const bool valid = i < npts;
+    double x = 0.0, y = 0.0, z = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (valid) {
+        const double *r = ref + (size_t)i * 3, *s = src + (size_t)i * 3;
+        x = r[0]; y = r[1]; z = r[2];
+        s0 = s[0]; s1 = s[1]; s2 = s[2];
+    }
+    const uint32_t m0 = blockIdx.y * (uint32_t)S3D_RANSAC_TILE;
+    const uint32_t nm = nmodels - m0 < (uint32_t)S3D_RANSAC_TILE ? nmodels - m0 : (uint32_t)S3D_RANSAC_TILE;
+    for (uint32_t j = 0; j < nm; j++) {
+        const double *A = models + (size_t)(m0 + j) * 12;
+        const double xo = A[0] * x + A[1] * y + A[2] * z + A[3];
+        const double yo = A[4] * x + A[5] * y + A[6] * z + A[7];
+        const double zo = A[8] * x + A[9] * y + A[10] * z + A[11];
+        const double e = (s0 - xo) * (s0 - xo) + (s1 - yo) * (s1 - yo) + (s2 - zo) * (s2 - zo);
+        const unsigned long long in = __ballot(valid && !(e > thr2));     /* the host's `if (e > thr2) continue;` */
+        if (lane == 0) s_part[wave][j] = __popcll(in);
+    }
+    __syncthreads();
+    if (tid < nm) {
+        const int c = s_part[0][tid] + s_part[1][tid] + s_part[2][tid] + s_part[3][tid];
+        if (c) atomicAdd(&counts[m0 + tid], c);
+    }
+}
+
+/* d_src, d_ref: npts x 3 row-major doubles; d_models: nmodels x 12 (3 x 4 row major); d_counts: nmodels ints, zeroed here. */
+extern "C" int s3d_k_ransac_count(const double *d_src, const double *d_ref, uint32_t npts, const double *d_models,
+                                  uint32_t nmodels, double thr2, int *d_counts, s3d_stream stream)
+{
+    if (npts < 1 || nmodels < 1) S3D_FAIL("bad dimensions");
+    if (npts > 0x7fffffffu) S3D_FAIL("too many matches for an int count");
+    const unsigned gy = s3d_div_up(nmodels, S3D_RANSAC_TILE);
+    if (gy > 65535u) S3D_FAIL("too many models for the scoring grid");
+    S3D_HIP(hipMemsetAsync(d_counts, 0, (size_t)nmodels * sizeof(int), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_ransac_count, dim3(s3d_div_up(npts, 256), gy), dim3(256), 0, (hipStream_t)stream, d_src, d_ref, npts,
+                       d_models, nmodels, thr2, d_counts);
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }

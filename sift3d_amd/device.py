@@ -40,6 +40,14 @@ def bind_extensions(L: C.CDLL) -> None:
     if hasattr(L, "sift3d_amd_set_mask"):
         L.sift3d_amd_set_mask.argtypes = [P(abi.SIFT3D), _vp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.sift3d_amd_have_mask.argtypes = [P(abi.SIFT3D)]
+    if hasattr(L, "sift3d_amd_set_ransac_device"):        # (absent from builds older than the device-scored RANSAC)
+        L.sift3d_amd_set_ransac_device.argtypes = [C.c_int]
+        L.sift3d_amd_get_ransac_device.argtypes = []
+        L.sift3d_amd_ransac_last_path.argtypes = []
+        L.sift3d_amd_set_ransac_profile.argtypes = [C.c_int]
+        L.sift3d_amd_set_ransac_profile.restype = None
+        L.sift3d_amd_ransac_last_device_ms.argtypes = []
+        L.sift3d_amd_ransac_last_device_ms.restype = C.c_double
 
 
 class DeviceLib:
@@ -91,6 +99,8 @@ class DeviceLib:
             L.s3d_k_select_scratch_bytes.argtypes = [C.c_uint32]
             L.s3d_k_select_scratch_bytes.restype = C.c_size_t
             L.s3d_k_select_strongest.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]
+        if hasattr(L, "s3d_k_ransac_count"):              # (absent from builds older than the device-scored RANSAC)
+            L.s3d_k_ransac_count.argtypes = [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -195,6 +205,14 @@ class DeviceLib:
         (float32, non-negative); ties go to the lower i (s3d_k_select_strongest)."""
         self.check(self.L.s3d_k_select_strongest(_vp(d_strength), _vp(d_keep), num, budget, _vp(d_scratch), _vp(stream)),
                    "s3d_k_select_strongest")
+
+    # --- RANSAC consensus counts -------------------------------------------------------------------------
+    def ransac_count(self, d_src: int, d_ref: int, npts: int, d_models: int, nmodels: int, thr2: float, d_counts: int,
+                     stream=None) -> None:
+        """d_counts[m] (int32) = number of matches i with !(|src_i - M_m [ref_i 1]^T|^2 > thr2), f64 (s3d_k_ransac_count):
+        d_src, d_ref npts x 3 and d_models nmodels x 12 doubles on the device."""
+        self.check(self.L.s3d_k_ransac_count(_vp(d_src), _vp(d_ref), npts, _vp(d_models), nmodels, thr2, _vp(d_counts),
+                                             _vp(stream)), "s3d_k_ransac_count")
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
