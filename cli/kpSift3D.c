@@ -2,11 +2,12 @@
  *
  * Same command line, outputs and messages as the reference program (cli/kpSift3D.c:1-228):
  *     kpSift3D [SIFT3D options] [--keys keys.csv] [--desc desc.csv] [--draw points.nii] [--mask mask.nii] [--max_keypoints N]
- *              image.nii
+ *              [--subvoxel] image.nii
  * linked against libsift3d_amd.so instead of libsift3D/libimutil.  Every call below is the reference's
  * API; detection and description run as HIP kernels, the rest is host C.  --mask is this program's own: keypoints inside a
  * region of interest only (sift3d_amd_set_mask); so is --max_keypoints: the N strongest keypoints only
- * (sift3d_amd_set_max_keypoints).
+ * (sift3d_amd_set_max_keypoints); and --subvoxel: positions and scales refined within their voxel and level
+ * (sift3d_amd_set_subvoxel).
  */
 #include <errno.h>
 #include <getopt.h>
@@ -39,6 +40,8 @@ static const char usage[] =
     "       Keeps the keypoints on non-zero voxels of this image (same dimensions) only. \n"
     " --max_keypoints [N] \n"
     "       Keeps the N keypoints of largest |DoG| response only (0: all). \n"
+    " --subvoxel \n"
+    "       Refines keypoint positions and scales by a quadratic fit to the DoG. \n"
     "\n";
 
 static void complain(const char *msg)
@@ -106,12 +109,13 @@ static unsigned char *read_mask(const char *path, int nx, int ny, int nz)
 
 int main(int argc, char *argv[])
 {
-    enum { OPT_KEYS = 'a', OPT_DESC, OPT_DRAW, OPT_MASK, OPT_MAXKP };
+    enum { OPT_KEYS = 'a', OPT_DESC, OPT_DRAW, OPT_MASK, OPT_MAXKP, OPT_SUBVOXEL };
     static const struct option outputs[] = {{"keys", required_argument, NULL, OPT_KEYS},
                                             {"desc", required_argument, NULL, OPT_DESC},
                                             {"draw", required_argument, NULL, OPT_DRAW},
                                             {"mask", required_argument, NULL, OPT_MASK},
                                             {"max_keypoints", required_argument, NULL, OPT_MAXKP},
+                                            {"subvoxel", no_argument, NULL, OPT_SUBVOXEL},
                                             {0, 0, 0, 0}};
     SIFT3D sift3d;
     Image im;
@@ -119,6 +123,7 @@ int main(int argc, char *argv[])
     SIFT3D_Descriptor_store desc;
     const char *keys_path = NULL, *desc_path = NULL, *draw_path = NULL, *mask_path = NULL;
     long max_keypoints = 0;
+    int subvoxel = 0;
 
     switch (parse_gnu(argc, argv)) {
     case SIFT3D_HELP:
@@ -151,6 +156,7 @@ int main(int argc, char *argv[])
                 return 1;
             }
         }
+        else if (c == OPT_SUBVOXEL) subvoxel = 1;
         else return 1;
     }
     if (!keys_path && !desc_path && !draw_path) {
@@ -186,6 +192,11 @@ int main(int argc, char *argv[])
     }
     if (sift3d_amd_set_max_keypoints(&sift3d, max_keypoints)) {
         complain_bug("Failed to set the keypoint budget.");
+        return 1;
+    }
+    /* (without the option the struct is left alone: SIFT3D_SUBVOXEL of the environment still decides) */
+    if (subvoxel && sift3d_amd_set_subvoxel(&sift3d, 1)) {
+        complain_bug("Failed to switch on sub-voxel refinement.");
         return 1;
     }
     if (SIFT3D_detect_keypoints(&sift3d, &im, &kp)) {

@@ -326,6 +326,20 @@ int s3d_k_key_strength(const s3d_pyramid_desc *pyr, const uint32_t *d_idx, const
 size_t s3d_k_select_scratch_bytes(uint32_t num);
 int s3d_k_select_strongest(const float *d_strength, uint32_t *d_keep, uint32_t num, uint32_t budget, void *d_scratch,
                            s3d_stream stream);
+/* Sub-voxel refinement (extension, sift3d_amd_set_subvoxel): offsets of the records d_xyzos[5i ..] = x, y, z, o, s (the layout
+ * s3d_k_compact_keys writes; s a pyramid level index, first_level included) from a quadratic fit to the DoG around each, D
+ * being the signed voxel s3d_k_key_strength takes the magnitude of, widened to f64:
+ *   g_a = (D(a+1) - D(a-1)) / 2,  H_aa = D(a+1) + D(a-1) - 2 D0,  H_ab = (D(a+1,b+1) - D(a+1,b-1) - D(a-1,b+1) + D(a-1,b-1)) / 4
+ * for a, b in x, y, z within DoG level s, and g_s, H_ss alike over the centre voxel of DoG levels s - 1, s + 1 (no space-scale
+ * cross terms).  Space: the solution of H3 d = -g3 if H3 or -H3 is positive definite (Sylvester) and every |d_a| <= 0.5 (flag
+ * bit 0); otherwise d_a = -g_a / H_aa per axis, clipped to [-0.5, 0.5], 0 where H_aa == 0 or the quotient is not finite (flag
+ * bit 1).  Scale: d_s = -g_s / H_ss under the same clip and zero rule.  d_off[4i ..] = d_x, d_y, d_z (octave voxels), d_s (levels).
+ * The number of records is read on the device: *d_num, at most max_num (the grid's bound), so a caller that has just compacted
+ * need not fetch the count first.  d_counters[0], [1]: how many records took the 3-D fit / the fallback; zeroed by the call.
+ * A record that cannot be refined -- a voxel outside 1 .. n - 2 of its octave, or a level without both DoG neighbours -- gets
+ * zero offsets and flag bit 2 and counts in neither; nothing is read for it.  One thread per record, all arithmetic f64. */
+int s3d_k_refine_keys(const s3d_pyramid_desc *pyr, const int32_t *d_xyzos, const uint32_t *d_num, uint32_t max_num,
+                      double *d_off, uint32_t *d_flags, uint32_t *d_counters, s3d_stream stream);
 
 /* One record per keypoint for the descriptor kernel; the scalar set-up mirrors
  * extract_descrip (sift.c:1845-1851) and is done on the host in the same float arithmetic. */

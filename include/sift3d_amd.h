@@ -527,6 +527,38 @@ int sift3d_amd_keypoint_strengths(SIFT3D *const sift3d, const Keypoint_store *co
  * budget the last two coincide).  NULLs, the default, record nothing. */
 void sift3d_amd_set_orient_events(void *before_orient, void *after_orient, void *after_select);
 
+/* ---- sub-voxel keypoints: position and scale refined by a quadratic fit to the DoG ---------------------------------------------
+ * Off by default: keypoints then sit on integer voxels of their octave and on pyramid levels, as the reference's do
+ * (detect_extrema, sift.c:1200-1205), and every output is what it was.  With refinement on, a detect returns exactly the list the
+ * same detect returns with it off -- same count, same order, same o, s and R (orientation is still assigned at the integer voxel) --
+ * in which xd, yd, zd have each moved by at most 0.5 octave voxels and sd has been multiplied by 2^(ds / num_kp_levels), |ds| <= 0.5.
+ * The fit per keypoint (x, y, z, o, s), D the DoG voxel as the reference stores it (sift3d_amd_download_pyramid(.., 1)), in f64:
+ *   gradient g_a = (D(a+1) - D(a-1)) / 2 and second differences H_aa, H_ab (the four diagonal neighbours / 4) over x, y, z within
+ *   level s; g_s and H_ss over the centre voxel of levels s - 1, s + 1.  No space-scale cross terms: at the coarse level spacing
+ *   they made positions worse.
+ *   Space: the solution of H3 d = -g3 where H3 or -H3 is positive definite and every |d_a| <= 0.5; otherwise the per-axis
+ *   parabolas d_a = -g_a / H_aa clipped to [-0.5, 0.5] (0 where H_aa == 0 or the quotient is not finite).
+ *   Scale: ds = -g_s / H_ss with the same clip and zero rule.
+ * xd = x + d_x (likewise yd, zd), sd = level scale * pow(2.0, ds / num_kp_levels).  Extrema lie in 1 .. n - 2 and keypoint levels
+ * have both DoG neighbours, so every read is inside the pyramid and every refined position passes SIFT3D_extract_descriptors'
+ * bounds check.  The kernel (s3d_k_refine_keys) runs behind the compaction on the compacted records, without a synchronisation of
+ * its own; a mask and a budget compose unchanged (both act before it).  Descriptors of refined keypoints are those of the refined
+ * doubles: the descriptor kernel takes centres off the grid.  sift3d_amd_keypoint_strengths truncates positions to a voxel: take
+ * strengths from an unrefined store.
+ * Applies to SIFT3D_detect_keypoints, sift3d_amd_detect_keypoints_dev and sift3d_amd_detect_keypoints_typed, the verbatim pass of
+ * non-finite volumes included, until it is changed.  Without a call the environment variable SIFT3D_SUBVOXEL (non-zero: on)
+ * decides, read once per struct at its first detect (for unchanged callers: register_SIFT3D, regSift3D); an explicit call
+ * overrides it.  copy_SIFT3D copies the setting.  With several GPUs (SIFT3D_NGPU > 1 / sift3d_amd_set_num_gpus) and refinement
+ * on a detect FAILS with a message that says so (the Z-slab ranks' gather carries integer records). */
+int sift3d_amd_set_subvoxel(SIFT3D *const sift3d, int on);
+int sift3d_amd_get_subvoxel(const SIFT3D *const sift3d);       /* 0 / 1: what the next detect on this struct will do */
+/* out[0] / out[1]: how many keypoints of the struct's last single-GPU detect took the 3-D fit / the per-axis fallback (their sum
+ * is the keypoint count; both 0 after an unrefined detect) */
+int sift3d_amd_last_subvoxel_counts(const SIFT3D *const sift3d, long out[2]);
+/* Profiling: HIP events the refining single-GPU detects of the calling thread record in front of and behind s3d_k_refine_keys
+ * (its counter reset included).  NULLs, the default, record nothing. */
+void sift3d_amd_set_subvoxel_events(void *before_refine, void *after_refine);
+
 /* ---- RANSAC: the hypotheses of find_tform_ransac scored on the device --------------------------------------------------------
  * find_tform_ransac draws its num_iter four-point models exactly as before (the same rand() calls in the same order; scoring
  * consumes none) and counts every model's inliers either in the host loop or in one kernel launch per batch of models

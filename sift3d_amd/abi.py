@@ -214,6 +214,46 @@ def keypoint_strengths(L: C.CDLL, sift3d, kp) -> np.ndarray:
     return out
 
 
+def set_subvoxel(L: C.CDLL, sift3d, on: bool) -> int:
+    """sift3d_amd_set_subvoxel: the following detects on ``sift3d`` refine every keypoint's position within its voxel and its
+    scale within its level by a quadratic fit to the DoG (same list, same order, same o, s and R); False restores integer
+    keypoints.  Overrides SIFT3D_SUBVOXEL of the environment.  Returns the C status."""
+    L.sift3d_amd_set_subvoxel.argtypes = [C.POINTER(SIFT3D), C.c_int]
+    L.sift3d_amd_set_subvoxel.restype = C.c_int
+    return L.sift3d_amd_set_subvoxel(C.byref(sift3d), 1 if on else 0)
+
+
+def get_subvoxel(L: C.CDLL, sift3d) -> bool:
+    L.sift3d_amd_get_subvoxel.argtypes = [C.POINTER(SIFT3D)]
+    L.sift3d_amd_get_subvoxel.restype = C.c_int
+    return bool(L.sift3d_amd_get_subvoxel(C.byref(sift3d)))
+
+
+def last_subvoxel_counts(L: C.CDLL, sift3d) -> tuple:
+    """sift3d_amd_last_subvoxel_counts: (keypoints that took the 3-D fit, keypoints that took the per-axis fallback) of the last
+    detect on ``sift3d``; (0, 0) after an unrefined one."""
+    L.sift3d_amd_last_subvoxel_counts.argtypes = [C.POINTER(SIFT3D), C.POINTER(C.c_long)]
+    L.sift3d_amd_last_subvoxel_counts.restype = C.c_int
+    out = (C.c_long * 2)()
+    if L.sift3d_amd_last_subvoxel_counts(C.byref(sift3d), out) != 0:
+        raise RuntimeError("sift3d_amd_last_subvoxel_counts failed")
+    return int(out[0]), int(out[1])
+
+
+def refined_keypoints_to_numpy(kp) -> tuple:
+    """(xyz float64 [K, 3] in octave voxels, o int32 [K], s int32 [K], sd float64 [K], R float32 [K, 3, 3]) of a store whose
+    positions may carry fractions (``Sift3dLib.keypoints_to_numpy`` is for integer records)."""
+    k = int(kp.slab.num)
+    xyz, o, s = np.zeros((k, 3), np.float64), np.zeros(k, np.int32), np.zeros(k, np.int32)
+    sd, R = np.zeros(k, np.float64), np.zeros((k, 3, 3), np.float32)
+    for i in range(k):
+        key = kp.buf[i]
+        xyz[i] = (key.xd, key.yd, key.zd)
+        o[i], s[i], sd[i] = key.o, key.s, key.sd
+        R[i] = np.array(key.r_data[:], dtype=np.float32).reshape(3, 3)
+    return xyz, o, s, sd, R
+
+
 def volume_to_numpy(v: Volume) -> np.ndarray:
     """A copy of a ``Volume``'s elements as [nz, ny, nx] in their stored type."""
     dt = {code: d for d, code in TYPED_DTYPES.items()}[v.dtype]

@@ -96,7 +96,7 @@ typedef struct {
     uint32_t *d_scratch;
     float *d_red;           /* small reduction slots: 64 words, see RED_* */
     uint32_t *d_count;      /* = d_red + RED_COUNT: [0] candidates, [1] keypoints, [2] orientation failed (a NaN window),
-                             * [4] work counter of the descriptor kernel */
+                             * [4] work counter of the descriptor kernel, [5] [6] counters of s3d_k_refine_keys */
     int verbatim;           /* the pass in flight runs on the literal kernels (a volume with non-finite voxels) */
     uint32_t cand_cap;
     uint32_t *d_cand_idx, *d_cand_tag, *d_keep;
@@ -144,9 +144,9 @@ typedef struct {
     void *inmax_ev[2];      /* [0]: the maximum exists (caller's stream), [1]: it has arrived (copy stream) */
     int inmax_pending;
     /* pinned host staging that lives with the context (a fresh malloc of a few MB per call is an mmap plus a page fault
-     * per 4 KB): [0] descriptor keys up, [1] keypoint coordinates down, [2] keypoint rotations down */
-    void *h_stage[3];
-    size_t h_stage_bytes[3];
+     * per 4 KB): [0] descriptor keys up, [1] keypoint coordinates down, [2] keypoint rotations down, [3] sub-voxel offsets down */
+    void *h_stage[4];
+    size_t h_stage_bytes[4];
     /* region of interest (sift3d_amd_set_mask).  Only the packed form is kept: one bit per voxel of every octave (bit i <->
      * linear voxel i, like the extrema bitmaps), the octaves one after the other in d_mask_bits -- about n / 7 bytes.  It
      * belongs to the struct, not to the pyramid: a detect on other dimensions fails, it does not drop the mask. */
@@ -162,6 +162,13 @@ typedef struct {
     uint32_t sel_cap;
     float *d_strength;
     void *d_select;
+    /* sub-voxel refinement (sift3d_amd_set_subvoxel): -1 unset (SIFT3D_SUBVOXEL of the environment decides, once per struct),
+     * 0 off, 1 on.  The offsets (four doubles per candidate slot) exist only on a struct that refines, sized with the
+     * candidate list; the two counters are words of d_count */
+    int subvoxel;
+    uint32_t refine_cap;
+    double *d_refine;
+    long subvoxel_counts[2];    /* of the last detect: keypoints that took the 3-D fit / the per-axis fallback */
 } s3d_ctx;
 
 /* words of c->d_red.  The input's maximum sits directly in front of the counters, so that the copy that fetches the
@@ -190,6 +197,7 @@ static int ctx_new(void)
             if (g_ctx[i]) {
                 g_ctx[i]->in_use = 1;
                 g_ctx[i]->host_pyramid = -1;
+                g_ctx[i]->subvoxel = -1;
                 h = i + 1;
             }
             break;
@@ -227,6 +235,8 @@ static void ctx_free_pyramid(s3d_ctx *c)
     dfree(&c->d_R); dfree(&c->d_Rk); dfree(&c->d_xyzos); dfree(&c->d_sigma); dfree(&c->d_orient); dfree(&c->d_oritab);
     dfree(&c->d_strength); dfree(&c->d_select);
     c->sel_cap = 0;
+    dfree(&c->d_refine);
+    c->refine_cap = 0;
     c->oritab_bytes = 0;
     c->nx = c->ny = c->nz = c->num_octaves = c->num_levels = 0;
     c->cand_cap = 0;
@@ -265,7 +275,7 @@ static void ctx_free_all(s3d_ctx *c)
     if (c->h_inmax) { s3d_rt_host_free(c->h_inmax); c->h_inmax = NULL; }
     for (int i = 0; i < 2; i++)
         if (c->inmax_ev[i]) { s3d_rt_event_destroy(c->inmax_ev[i]); c->inmax_ev[i] = NULL; }
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < 4; i++) {
         if (c->h_stage[i]) s3d_rt_host_free(c->h_stage[i]);
         c->h_stage[i] = NULL;
         c->h_stage_bytes[i] = 0;
@@ -564,6 +574,31 @@ static int ctx_ensure_candidates(s3d_ctx *c, uint32_t cap)
     DEV(s3d_rt_malloc(&c->d_orient, s3d_k_orient_scratch_bytes(cap)));
     c->cand_cap = cap;
     return ctx_ensure_select(c, cap);
+}
+
+/* 0 / 1: see s3d_ctx.subvoxel; unset -> SIFT3D_SUBVOXEL of the environment, read once per struct */
+static int subvoxel_env(void)
+{
+    const char *e = getenv("SIFT3D_SUBVOXEL");
+    return e != NULL && atoi(e) != 0;
+}
+
+static int subvoxel_mode(s3d_ctx *c)
+{
+    if (c->subvoxel < 0) c->subvoxel = subvoxel_env();
+    return c->subvoxel;
+}
+
+/* the offsets and flags of `cap` records (s3d_k_refine_keys: four doubles, then one word each): only a struct that refines
+ * pays for them */
+static int ctx_ensure_refine(s3d_ctx *c, uint32_t cap)
+{
+    if (c->refine_cap >= cap) return SIFT3D_SUCCESS;
+    dfree(&c->d_refine);
+    c->refine_cap = 0;
+    DEV(s3d_rt_malloc((void **)&c->d_refine, (size_t)cap * (4 * sizeof(double) + sizeof(uint32_t))));
+    c->refine_cap = cap;
+    return SIFT3D_SUCCESS;
 }
 
 static void fill_pyr_desc(const Pyramid *g, float *const *levels, s3d_pyramid_desc *pd)
@@ -940,15 +975,23 @@ void sift3d_amd_set_orient_events(void *before_orient, void *after_orient, void 
     g_orient_ev[0] = before_orient; g_orient_ev[1] = after_orient; g_orient_ev[2] = after_select;
 }
 
+/* profiling (scripts/subvoxel_cost.py): HIP events either side of s3d_k_refine_keys, likewise */
+static __thread void *g_refine_ev[2];
+void sift3d_amd_set_subvoxel_events(void *before_refine, void *after_refine)
+{
+    g_refine_ev[0] = before_refine; g_refine_ev[1] = after_refine;
+}
+
 /* detect_extrema (sift.c:1074-1212) + assign_orientations (sift.c:1264-1325) on the device */
 static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp)
 {
     const Pyramid *g = &sift3d->gpyr;
     const int L = g->num_levels;
     s3d_pyramid_desc pd;
-    uint32_t counts[3] = {0, 0, 0};
+    uint32_t counts[7] = {0, 0, 0, 0, 0, 0, 0};           /* c->d_count's words */
     uint32_t inmax_count[2] = {0, 0};
     uint32_t cap = candidate_capacity(c);
+    const int refine = subvoxel_mode(c);
     for (int attempt = 0; attempt < 2; attempt++) {
         s3d_stream es = c->stream;
         if (attempt == 0 && c->extrema_enqueued) {
@@ -972,6 +1015,7 @@ static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp
         if (attempt == 1) API_FAIL("sift3d_amd: candidate buffer overflow");
     }
     c->last_num_candidates = (long)counts[0];
+    c->subvoxel_counts[0] = c->subvoxel_counts[1] = 0;
 
     /* keypoint store metadata: dims of the first DoG keypoint level = octave 0 (sift.c:1096-1099) */
     kp->nx = g->levels->nx; kp->ny = g->levels->ny; kp->nz = g->levels->nz;
@@ -1008,8 +1052,19 @@ static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp
         if (g_orient_ev[2]) DEV(s3d_rt_event_record(g_orient_ev[2], c->stream));
         DEV(s3d_k_compact_keys(&pd, c->d_cand_idx, c->d_cand_tag, c->d_R, c->d_keep, counts[0], c->d_xyzos,
                                c->d_Rk, c->d_count + 1, c->d_kscratch, c->stream));
-        DEV(s3d_rt_d2h(counts + 1, c->d_count + 1, 2 * sizeof(uint32_t), c->stream));
+        if (refine) {
+            /* sub-voxel offsets of the compacted records: the kernel reads their number where the compaction left it, so the
+             * launch needs no round trip -- its grid covers the candidates, the threads past the count leave at once */
+            if (ctx_ensure_refine(c, c->cand_cap)) return SIFT3D_FAILURE;
+            if (g_refine_ev[0]) DEV(s3d_rt_event_record(g_refine_ev[0], c->stream));
+            DEV(s3d_k_refine_keys(&pd, c->d_xyzos, c->d_count + 1, counts[0], c->d_refine,
+                                  (uint32_t *)(c->d_refine + 4 * (size_t)c->refine_cap), c->d_count + 5, c->stream));
+            if (g_refine_ev[1]) DEV(s3d_rt_event_record(g_refine_ev[1], c->stream));
+        }
+        DEV(s3d_rt_d2h(counts + 1, c->d_count + 1, (refine ? 6 : 2) * sizeof(uint32_t), c->stream));
         DEV(s3d_rt_sync(c->stream));
+        c->subvoxel_counts[0] = (long)counts[5];
+        c->subvoxel_counts[1] = (long)counts[6];
         if (counts[2]) {
             /* a candidate's window holds a NaN gradient: the reference's eigen_Mat_rm fails there and the call with it */
             API_FAIL("sift3d_amd: a NaN voxel inside a keypoint candidate's orientation window (the reference's "
@@ -1020,13 +1075,17 @@ static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp
         const uint32_t K = counts[1];
         int32_t *xyzos;
         float *R;
+        double *off = NULL;
+        const double nkp = (double)g->num_kp_levels;
         if (resize_Keypoint_store(kp, K)) return SIFT3D_FAILURE;
         if (K == 0) return SIFT3D_SUCCESS;
         if (ctx_stage(c, 1, (size_t)K * 5 * sizeof(int32_t), (void **)&xyzos) ||
-            ctx_stage(c, 2, (size_t)K * 9 * sizeof(float), (void **)&R))
+            ctx_stage(c, 2, (size_t)K * 9 * sizeof(float), (void **)&R) ||
+            (refine && ctx_stage(c, 3, (size_t)K * 4 * sizeof(double), (void **)&off)))
             return SIFT3D_FAILURE;
         if (s3d_rt_d2h(xyzos, c->d_xyzos, (size_t)K * 5 * sizeof(int32_t), c->stream) ||
-            s3d_rt_d2h(R, c->d_Rk, (size_t)K * 9 * sizeof(float), c->stream) || s3d_rt_sync(c->stream))
+            s3d_rt_d2h(R, c->d_Rk, (size_t)K * 9 * sizeof(float), c->stream) ||
+            (refine && s3d_rt_d2h(off, c->d_refine, (size_t)K * 4 * sizeof(double), c->stream)) || s3d_rt_sync(c->stream))
             API_FAIL("sift3d_amd: keypoint download failed: %s", s3d_rt_last_error());
         for (uint32_t i = 0; i < K; i++) {
             Keypoint *key = kp->buf + i;
@@ -1038,6 +1097,14 @@ static int detect_dev(SIFT3D *const sift3d, s3d_ctx *c, Keypoint_store *const kp
             key->s = xyzos[5 * i + 4];
             key->sd = SIFT3D_PYR_IM_GET(&sift3d->dog, key->o, key->s)->s;
             memcpy(key->r_data, R + 9 * i, 9 * sizeof(float));
+            if (refine) {
+                /* the fit moves the position within its voxel and the scale within its level; o, s and R -- assigned at the
+                 * integer voxel -- stay */
+                key->xd += off[4 * i + 0];
+                key->yd += off[4 * i + 1];
+                key->zd += off[4 * i + 2];
+                key->sd *= pow(2.0, off[4 * i + 3] / nkp);
+            }
         }
     }
     return SIFT3D_SUCCESS;
@@ -1200,6 +1267,40 @@ static int budget_check_single_gpu(const SIFT3D *sift3d)
              "clear it with 0 or detect on one GPU", c->max_keypoints);
 }
 
+/* ---- sub-voxel refinement (include/sift3d_amd.h) ---------------------------------------------------------------------------- */
+int sift3d_amd_set_subvoxel(SIFT3D *const sift3d, int on)
+{
+    if (sift3d == NULL) API_FAIL("sift3d_amd_set_subvoxel: null argument");
+    if (!sift3d->kernels.downsample_2 && !(sift3d->kernels.downsample_2 = ctx_new()))
+        API_FAIL("sift3d_amd: out of device contexts");
+    sift_ctx(sift3d)->subvoxel = on != 0;                  /* an explicit call overrides the environment */
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_get_subvoxel(const SIFT3D *const sift3d)
+{
+    s3d_ctx *c = sift3d ? sift_ctx(sift3d) : NULL;
+    return c ? subvoxel_mode(c) : subvoxel_env();          /* (a struct without a context takes the environment's when it detects) */
+}
+
+int sift3d_amd_last_subvoxel_counts(const SIFT3D *const sift3d, long out[2])
+{
+    const s3d_ctx *c = sift3d ? sift_ctx(sift3d) : NULL;
+    if (out == NULL) API_FAIL("sift3d_amd_last_subvoxel_counts: null argument");
+    out[0] = c ? c->subvoxel_counts[0] : 0;
+    out[1] = c ? c->subvoxel_counts[1] : 0;
+    return SIFT3D_SUCCESS;
+}
+
+/* the Z-slab ranks' gather carries integer records: refinement with several GPUs fails, it is not silently ignored */
+static int subvoxel_check_single_gpu(const SIFT3D *sift3d)
+{
+    s3d_ctx *c = sift_ctx(sift3d);
+    if (c == NULL || !subvoxel_mode(c)) return SIFT3D_SUCCESS;
+    API_FAIL("sift3d_amd: sub-voxel refinement (sift3d_amd_set_subvoxel / SIFT3D_SUBVOXEL) is not supported with several GPUs; "
+             "switch it off with 0 or detect on one GPU");
+}
+
 /* a detect on a volume of other dimensions than the mask's fails: the mask is not silently ignored */
 static int mask_check_dims(const SIFT3D *sift3d, int nx, int ny, int nz)
 {
@@ -1263,7 +1364,8 @@ int SIFT3D_detect_keypoints(SIFT3D *const sift3d, const Image *const im, Keypoin
     }
     if (mgpu_for(sift3d) > 1) {                            /* Z-slabs over several GPUs (s3d_host_slab.c) */
         s3d_ctx *c = sift_ctx(sift3d);
-        if (budget_check_single_gpu(sift3d) || mask_check_dims(sift3d, im->nx, im->ny, im->nz)) {
+        if (budget_check_single_gpu(sift3d) || subvoxel_check_single_gpu(sift3d) ||
+            mask_check_dims(sift3d, im->nx, im->ny, im->nz)) {
             free(dense);
             return SIFT3D_FAILURE;
         }
@@ -1798,6 +1900,7 @@ int copy_SIFT3D(const SIFT3D *const src, SIFT3D *const dst)
         dc->mask_noct = sc->mask_noct;
     }
     if (sc != NULL && sc->max_keypoints > 0 && sift3d_amd_set_max_keypoints(dst, sc->max_keypoints)) return SIFT3D_FAILURE;
+    if (sc != NULL && sc->subvoxel >= 0 && sift3d_amd_set_subvoxel(dst, sc->subvoxel)) return SIFT3D_FAILURE;
     if (sc == NULL || sc->d_im == NULL || src->im.nx <= 0 || sc->pyramid_on_slabs)
         return SIFT3D_SUCCESS;                            /* no image yet (a multi-GPU pyramid is not copied: parameters only) */
     {

@@ -922,6 +922,91 @@ extern "C" int s3d_k_key_strength(const s3d_pyramid_desc *pyr, const uint32_t *d
     return S3D_OK;
 }
 
+/* ---- sub-voxel refinement of compacted keypoints (extension: sift3d_amd_set_subvoxel) -------------------
+ * Lowe's quadratic fit around the extremum, separable: a 3-D fit in space within the keypoint's own DoG level and an
+ * independent parabola through the centre voxel of the levels either side (the space-scale cross terms do harm at the
+ * coarse level spacing).  D is the DoG voxel of k_key_strength with the sign build_dog gives it (the offsets do not depend
+ * on that sign: it flips g and H together), widened to f64; everything after is f64 and
+ * this file is compiled without contraction.  A record reads 19 voxels of GSS levels k and k + 1 and the centre voxel of
+ * levels k - 1 and k + 2.  Records come from the detector (extrema lie in 1 .. n - 2 and keypoint levels have both DoG
+ * neighbours) or from a caller: one that is not refinable is left alone (flag bit 2), never read out of bounds. */
+__device__ __forceinline__ double refine_axis(double g, double h)
+{
+    const double v = -g / h;
+    if (h == 0.0 || !__builtin_isfinite(v)) return 0.0;
+    return v < -0.5 ? -0.5 : v > 0.5 ? 0.5 : v;
+}
+
+__global__ void __launch_bounds__(256)
+k_refine_keys(s3d_pyramid_desc pyr, const int32_t *__restrict__ xyzos, const uint32_t *__restrict__ d_num, uint32_t max_num,
+              double *__restrict__ d_off, uint32_t *__restrict__ d_flags, uint32_t *__restrict__ d_counters)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= max_num || i >= *d_num) return;
+    const int x = xyzos[5 * i + 0], y = xyzos[5 * i + 1], z = xyzos[5 * i + 2], o = xyzos[5 * i + 3];
+    const int k = xyzos[5 * i + 4] - pyr.first_level;
+    double dx = 0.0, dy = 0.0, dz = 0.0, ds = 0.0;
+    uint32_t flag = 4u;
+    if (o >= 0 && o < pyr.num_octaves && k >= 1 && k + 2 < pyr.num_levels && x >= 1 && y >= 1 && z >= 1 &&
+        x <= pyr.dims[o][0] - 2 && y <= pyr.dims[o][1] - 2 && z <= pyr.dims[o][2] - 2) {
+        const ptrdiff_t nx = pyr.dims[o][0], plane = nx * (ptrdiff_t)pyr.dims[o][1];
+        const ptrdiff_t c = (ptrdiff_t)z * plane + (ptrdiff_t)y * nx + (ptrdiff_t)x;
+        const float *const *lv = pyr.d_level + o * pyr.num_levels + k;
+        const float *__restrict__ A = lv[0], *__restrict__ B = lv[1];
+#define RF_D(off) ((double)(A[c + (off)] - B[c + (off)]))       /* one f32 subtraction, level s minus level s + 1: build_dog */
+        const double d0 = RF_D(0);
+        const double xm = RF_D(-1), xp = RF_D(1), ym = RF_D(-nx), yp = RF_D(nx), zm = RF_D(-plane), zp = RF_D(plane);
+        const double hxy = 0.25 * (RF_D(nx + 1) - RF_D(1 - nx) - RF_D(nx - 1) + RF_D(-nx - 1));
+        const double hxz = 0.25 * (RF_D(plane + 1) - RF_D(1 - plane) - RF_D(plane - 1) + RF_D(-plane - 1));
+        const double hyz = 0.25 * (RF_D(plane + nx) - RF_D(nx - plane) - RF_D(plane - nx) + RF_D(-plane - nx));
+#undef RF_D
+        const double sm = (double)(lv[-1][c] - A[c]), sp = (double)(B[c] - lv[2][c]);
+        const double gx = 0.5 * (xp - xm), gy = 0.5 * (yp - ym), gz = 0.5 * (zp - zm), gs = 0.5 * (sp - sm);
+        const double hxx = xp + xm - 2.0 * d0, hyy = yp + ym - 2.0 * d0, hzz = zp + zm - 2.0 * d0, hss = sp + sm - 2.0 * d0;
+        /* H3 delta = -g3 by cofactors; H3 or -H3 positive definite (Sylvester): the second leading minor is the same for
+         * both, the first and the third change sign together */
+        const double c00 = hyy * hzz - hyz * hyz, c01 = hxz * hyz - hxy * hzz, c02 = hxy * hyz - hxz * hyy;
+        const double c11 = hxx * hzz - hxz * hxz, c12 = hxy * hxz - hxx * hyz, c22 = hxx * hyy - hxy * hxy;
+        const double det = hxx * c00 + hxy * c01 + hxz * c02;
+        const bool definite = c22 > 0.0 && ((hxx > 0.0 && det > 0.0) || (hxx < 0.0 && det < 0.0));
+        const double fx = -(c00 * gx + c01 * gy + c02 * gz) / det;
+        const double fy = -(c01 * gx + c11 * gy + c12 * gz) / det;
+        const double fz = -(c02 * gx + c12 * gy + c22 * gz) / det;
+        if (definite && fabs(fx) <= 0.5 && fabs(fy) <= 0.5 && fabs(fz) <= 0.5) {    /* (false for a NaN or an infinity) */
+            dx = fx; dy = fy; dz = fz;
+            flag = 1u;
+        } else {                                          /* per-axis parabolas, clipped to the voxel */
+            dx = refine_axis(gx, hxx); dy = refine_axis(gy, hyy); dz = refine_axis(gz, hzz);
+            flag = 2u;
+        }
+        ds = refine_axis(gs, hss);
+    }
+    d_off[4 * i + 0] = dx; d_off[4 * i + 1] = dy; d_off[4 * i + 2] = dz; d_off[4 * i + 3] = ds;
+    d_flags[i] = flag;
+    /* the counters: one integer atomic per wave and counter, from the lowest lane still here (one per record on two
+     * addresses serialises in the L2: 0.29 ms for the 31 207 records of the 512^3 benchmark volume against 0.03 ms
+     * this way, profiles/subvoxel_cost.txt) */
+    const unsigned long long here = __ballot(1), fit = __ballot(flag == 1u), fall = __ballot(flag == 2u);
+    if ((threadIdx.x & 63u) == (unsigned)(__ffsll((long long)here) - 1)) {
+        if (fit) atomicAdd(d_counters, (uint32_t)__popcll(fit));
+        if (fall) atomicAdd(d_counters + 1, (uint32_t)__popcll(fall));
+    }
+}
+
+extern "C" int s3d_k_refine_keys(const s3d_pyramid_desc *pyr, const int32_t *d_xyzos, const uint32_t *d_num, uint32_t max_num,
+                                 double *d_off, uint32_t *d_flags, uint32_t *d_counters, s3d_stream stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (d_num == nullptr || d_counters == nullptr) S3D_FAIL("s3d_k_refine_keys: the count and the counters live on the device");
+    S3D_HIP(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), st));
+    if (max_num == 0) return S3D_OK;
+    if (d_xyzos == nullptr || d_off == nullptr || d_flags == nullptr) S3D_FAIL("s3d_k_refine_keys: null record or output array");
+    hipLaunchKernelGGL(k_refine_keys, dim3(s3d_div_up(max_num, 256)), dim3(256), 0, st, *pyr, d_xyzos, d_num, max_num, d_off,
+                       d_flags, d_counters);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
 /* What the finished histograms hist[0 .. npass) say: out[0] = the digits chosen so far (npass * 8 bits), out[1] = how many
  * entries matching them are still to be kept (>= 1), out[2] = 0 iff no more entries are kept than `budget` (nothing to
  * do).  Pass p's digit is the largest d with  #(digit > d) < k <= #(digit >= d)  among the entries matching the digits

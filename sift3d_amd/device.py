@@ -48,6 +48,10 @@ def bind_extensions(L: C.CDLL) -> None:
         L.sift3d_amd_set_ransac_profile.restype = None
         L.sift3d_amd_ransac_last_device_ms.argtypes = []
         L.sift3d_amd_ransac_last_device_ms.restype = C.c_double
+    if hasattr(L, "sift3d_amd_set_subvoxel"):             # (absent from builds older than the sub-voxel refinement)
+        L.sift3d_amd_set_subvoxel.argtypes = [P(abi.SIFT3D), C.c_int]
+        L.sift3d_amd_get_subvoxel.argtypes = [P(abi.SIFT3D)]
+        L.sift3d_amd_last_subvoxel_counts.argtypes = [P(abi.SIFT3D), P(C.c_long)]
 
 
 class DeviceLib:
@@ -101,6 +105,8 @@ class DeviceLib:
             L.s3d_k_select_strongest.argtypes = [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]
         if hasattr(L, "s3d_k_ransac_count"):              # (absent from builds older than the device-scored RANSAC)
             L.s3d_k_ransac_count.argtypes = [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, _vp, _vp]
+        if hasattr(L, "s3d_k_refine_keys"):               # (absent from builds older than the sub-voxel refinement)
+            L.s3d_k_refine_keys.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -205,6 +211,15 @@ class DeviceLib:
         (float32, non-negative); ties go to the lower i (s3d_k_select_strongest)."""
         self.check(self.L.s3d_k_select_strongest(_vp(d_strength), _vp(d_keep), num, budget, _vp(d_scratch), _vp(stream)),
                    "s3d_k_select_strongest")
+
+    # --- sub-voxel refinement ----------------------------------------------------------------------------
+    def refine_keys(self, pyr_desc, d_xyzos: int, d_num: int, max_num: int, d_off: int, d_flags: int, d_counters: int,
+                    stream=None) -> None:
+        """Offsets (4 float64 per record: dx, dy, dz in octave voxels, ds in levels), flag words (uint32) and the two
+        counters of the *d_num <= max_num records d_xyzos (int32 x, y, z, o, s) -- s3d_k_refine_keys.  ``pyr_desc``: a
+        ctypes image of s3d_pyramid_desc (include/s3d_device.h), passed by reference."""
+        self.check(self.L.s3d_k_refine_keys(C.byref(pyr_desc), _vp(d_xyzos), _vp(d_num), max_num, _vp(d_off), _vp(d_flags),
+                                            _vp(d_counters), _vp(stream)), "s3d_k_refine_keys")
 
     # --- RANSAC consensus counts -------------------------------------------------------------------------
     def ransac_count(self, d_src: int, d_ref: int, npts: int, d_models: int, nmodels: int, thr2: float, d_counts: int,
