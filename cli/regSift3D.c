@@ -4,6 +4,8 @@
  * Same command line, outputs and messages as the reference program (cli/regSift3D.c:1-485):
  *     regSift3D [SIFT3D options] [--matches m.csv] [--transform t.csv] [--warped w.nii] [--nn_thresh v]
  *               [--err_thresh v] [--num_iter n] [--type affine] [--resample] source.nii reference.nii
+ * and, beyond the reference, [--tps] [--tps_lambda v] [--tps_thresh v] [--tps_max_points n]: a thin-plate spline fitted to
+ * the matches near the affine map (sift3d_amd_register_tps), written by --transform and used by --warped,
  * linked against libsift3d_amd.so.  Detection, description, matching and the warp run as HIP kernels;
  * RANSAC is host C.  As in the reference, --err_thresh and --num_iter are parsed after the Ransac
  * parameters have been copied into the registration object, so they do not reach the estimator
@@ -44,6 +46,20 @@ static void usage(void)
            "       Supported file formats: .nii, .nii.gz \n"
            "At least one output option must be specified. \n"
            "\n"
+           "Thin-plate-spline options: \n"
+           " --tps - After the affine fit, fit a thin-plate spline to the \n"
+           "       matches that agree with it. --transform then writes the \n"
+           "       spline (one row [x y z wx wy wz] per control point, then \n"
+           "       four rows [0 0 0 ax ay az]: the constant and the x, y, z \n"
+           "       coefficients) and --warped warps with it. \n"
+           " --tps_lambda [value] - Smoothing weight, in the interval \n"
+           "       [0, inf). 0 interpolates the matches. (default: %.0f) \n"
+           " --tps_thresh [value] - Matches within this distance of the \n"
+           "       affine fit, in real-world units, become control points. \n"
+           "       (default: 4 x err_thresh) \n"
+           " --tps_max_points [value] - Largest number of control points. \n"
+           "       (default: %d) \n"
+           "\n"
            "Other options: \n"
            " --nn_thresh [value] - Matching threshold on the nearest neighbor \n"
            "       ratio, in the interval (0, 1]. (default: %.2f) \n"
@@ -58,7 +74,8 @@ static void usage(void)
            "	have very different resolutions, for example registering 5mm \n"
            "	to 1mm slices. \n"
            "\n",
-           SIFT3D_nn_thresh_default, SIFT3D_err_thresh_default, SIFT3D_num_iter_default);
+           SIFT3D_AMD_TPS_LAMBDA_DEFAULT, SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT, SIFT3D_nn_thresh_default,
+           SIFT3D_err_thresh_default, SIFT3D_num_iter_default);
     print_opts_SIFT3D();
 }
 
@@ -82,7 +99,8 @@ static void complain_path(const char *what, const char *path)
 
 int main(int argc, char *argv[])
 {
-    enum { MATCHES = 'a', TRANSFORM, WARPED, CONCAT, KEYS, LINES, NN_THRESH, ERR_THRESH, NUM_ITER, TYPE, RESAMPLE };
+    enum { MATCHES = 'a', TRANSFORM, WARPED, CONCAT, KEYS, LINES, NN_THRESH, ERR_THRESH, NUM_ITER, TYPE, RESAMPLE, TPS_FIT, TPS_LAMBDA,
+           TPS_THRESH, TPS_MAX_POINTS };
     static const struct option longopts[] = {{"matches", required_argument, NULL, MATCHES},
                                              {"transform", required_argument, NULL, TRANSFORM},
                                              {"warped", required_argument, NULL, WARPED},
@@ -94,6 +112,10 @@ int main(int argc, char *argv[])
                                              {"num_iter", required_argument, NULL, NUM_ITER},
                                              {"type", required_argument, NULL, TYPE},
                                              {"resample", no_argument, NULL, RESAMPLE},
+                                             {"tps", no_argument, NULL, TPS_FIT},
+                                             {"tps_lambda", required_argument, NULL, TPS_LAMBDA},
+                                             {"tps_thresh", required_argument, NULL, TPS_THRESH},
+                                             {"tps_max_points", required_argument, NULL, TPS_MAX_POINTS},
                                              {0, 0, 0, 0}};
     Reg_SIFT3D reg;
     SIFT3D sift3d;
@@ -101,9 +123,11 @@ int main(int argc, char *argv[])
     Image src, ref;
     Mat_rm match_src, match_ref;
     Affine tform;
+    Tps tps;
+    sift3d_amd_tps_opts tps_opts = {-1.0, 0.0, 0};     /* the library's defaults */
     const char *match_path = NULL, *tform_path = NULL, *warped_path = NULL, *concat_path = NULL, *keys_path = NULL,
                *lines_path = NULL;
-    int have_match = 0, have_tform = 0, resample = 0;
+    int have_match = 0, have_tform = 0, resample = 0, use_tps = 0;
 
     switch (parse_gnu(argc, argv)) {
     case SIFT3D_HELP: usage(); return 0;
@@ -152,6 +176,19 @@ int main(int argc, char *argv[])
             }
             break;
         case RESAMPLE: resample = 1; break;
+        case TPS_FIT: use_tps = 1; break;
+        case TPS_LAMBDA:
+            tps_opts.lambda = atof(optarg);
+            if (!(tps_opts.lambda >= 0.0)) { complain("Invalid value for tps_lambda."); return 1; }
+            break;
+        case TPS_THRESH:
+            tps_opts.ctrl_thresh = atof(optarg);
+            if (!(tps_opts.ctrl_thresh > 0.0)) { complain("Invalid value for tps_thresh."); return 1; }
+            break;
+        case TPS_MAX_POINTS:
+            tps_opts.max_points = atoi(optarg);
+            if (tps_opts.max_points < 4) { complain("Invalid value for tps_max_points."); return 1; }
+            break;
         default: return 1;
         }
     }
@@ -159,7 +196,9 @@ int main(int argc, char *argv[])
     if (argc - optind < 2) { complain("Not enough arguments."); return 1; }
     if (argc - optind > 2) { complain("Too many arguments."); return 1; }
     const char *src_path = argv[optind], *ref_path = argv[optind + 1];
-    if (init_tform(&tform, AFFINE)) return 1;
+    if (use_tps && resample) { complain("--tps cannot be combined with --resample."); return 1; }
+    use_tps = use_tps && have_tform;                   /* the spline only shows in --transform and --warped */
+    if (init_tform(&tform, AFFINE) || init_Tps(&tps, IM_NDIMS, IM_NDIMS + 1)) return 1;
     if (im_read(src_path, &src)) { complain_path("Failed to read the source image", src_path); return 1; }
     if (im_read(ref_path, &ref)) { complain_path("Failed to read the reference image", ref_path); return 1; }
     void *const tform_arg = have_tform ? (void *)&tform : NULL;
@@ -171,7 +210,13 @@ int main(int argc, char *argv[])
     } else {
         if (set_src_Reg_SIFT3D(&reg, &src)) { complain("Failed to set the source image."); return 1; }
         if (set_ref_Reg_SIFT3D(&reg, &ref)) { complain("Failed to set the reference image."); return 1; }
-        if (register_SIFT3D(&reg, tform_arg)) { complain("Failed to register the images."); return 1; }
+        if (use_tps) {
+            if (sift3d_amd_register_tps(&reg, &tps_opts, &tform, &tps)) {
+                fprintf(stderr, "%s\n", sift3d_amd_last_error());
+                complain("Failed to register the images with a thin-plate spline.");
+                return 1;
+            }
+        } else if (register_SIFT3D(&reg, tform_arg)) { complain("Failed to register the images."); return 1; }
     }
     if (get_matches_Reg_SIFT3D(&reg, &match_src, &match_ref)) {
         complain_bug("Failed to convert matches to coordinates.");
@@ -184,7 +229,8 @@ int main(int argc, char *argv[])
         if (write_Mat_rm(match_path, &matches)) { complain_path("Failed to write the matches", match_path); return 1; }
         cleanup_Mat_rm(&matches);
     }
-    if (tform_path != NULL && write_tform(tform_path, &tform)) {
+    const void *const tform_out = use_tps ? (const void *)&tps : (const void *)&tform;
+    if (tform_path != NULL && write_tform(tform_path, tform_out)) {
         complain_path("Failed to write the transformation parameters", tform_path);
         return 1;
     }
@@ -192,7 +238,7 @@ int main(int argc, char *argv[])
         Image warped;
         init_im(&warped);
         if (im_copy_dims(&ref, &warped)) { complain_bug("Failed to resize the warped image."); return 1; }
-        if (im_inv_transform(&tform, &src, LINEAR, SIFT3D_FALSE, &warped)) { complain_bug("Failed to warp the source image."); return 1; }
+        if (im_inv_transform(tform_out, &src, LINEAR, SIFT3D_FALSE, &warped)) { complain_bug("Failed to warp the source image."); return 1; }
         if (im_write(warped_path, &warped)) { complain_path("Failed to write the warped image", warped_path); return 1; }
         im_free(&warped);
     }
@@ -223,6 +269,7 @@ int main(int argc, char *argv[])
         cleanup_Mat_rm(&keys_src); cleanup_Mat_rm(&keys_ref);
     }
     cleanup_tform(&tform);
+    cleanup_tform(&tps);
     cleanup_Mat_rm(&match_src);
     cleanup_Mat_rm(&match_ref);
     cleanup_Reg_SIFT3D(&reg);

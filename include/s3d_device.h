@@ -424,6 +424,18 @@ int s3d_k_dense_post(float *d_desc12, const float *d_in, size_t nvox, s3d_stream
 int s3d_k_inv_affine(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny, int dnz,
                      const double A[12], int interp, s3d_stream stream);
 
+/* ---- inverse thin-plate-spline warp (s3d_resample.hip; im_inv_transform through apply_Tps_xyz, imutil.c:2676-2729) --------
+ * d_dst(x,y,z,c) = sample of d_src at f(x,y,z) = sum_n U(r2_n) w_n + a_0 + a_x x + a_y y + a_z z in f64, U(r2) = r2 log r2 and
+ * U(0) = 0, r2_n the squared distance to control point n.  d_ctrl: n_ctrl x 3 row major; d_params: 3 x (n_ctrl + 4) row major
+ * (row r: the n_ctrl weights of output coordinate r, its constant, its x, y, z coefficients).  Control points are summed in
+ * ascending order, then the constant, then the x, y, z terms, each its own separately rounded multiplication and addition, so
+ * n_ctrl = 0 (d_ctrl may be NULL) is bit-identical to the reference; the kernel sum uses fused multiply-adds and the device's
+ * log.  Sampling, the zero outside the source and the NaN rule are s3d_k_inv_affine's.  Any n_ctrl: the control points are
+ * streamed through LDS S3D_TPS_TILE at a time. */
+#define S3D_TPS_TILE 128                 /* control points per LDS tile */
+int s3d_k_inv_tps(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny, int dnz,
+                  const double *d_ctrl, const double *d_params, uint32_t n_ctrl, int interp, s3d_stream stream);
+
 /* ---- RANSAC consensus counts (s3d_resample.hip; the scoring loop of find_tform_ransac, imutil.c:4527-4552, 4802-4815) ----
  * counts[m] = #{ i < npts : !(e(i,m) > thr2) },  e = |src_i - M_m [ref_i 1]^T|^2 in f64 with the host loop's operation order
  * (x' = A0*x + A1*y + A2*z + A3 left to right, no contraction), so a NaN e counts and e == thr2 counts.  d_src, d_ref: npts x 3

@@ -308,6 +308,12 @@ typedef struct _Affine {
     Tform tform;
     Mat_rm A;                          /* dim x (dim+1) doubles: x' = A [x 1]^T */
 } Affine;
+typedef struct _Tps {                  /* imtypes.h:380-385 */
+    Tform tform;
+    Mat_rm params;                     /* dim x (N + dim + 1) doubles: N kernel weights, the constant, the x, y, z coefficients */
+    Mat_rm kp_src;                     /* N x dim doubles: the control points */
+    int dim;
+} Tps;
 typedef struct _Ransac {
     double err_thresh;                 /* inlier threshold (its square bounds the squared error) */
     int num_iter;
@@ -330,6 +336,9 @@ int copy_Ransac(const Ransac *const src, Ransac *const dst);             /* imut
 int init_Affine(Affine *const affine, const int dim);                    /* imutil.c:2560 */
 int Affine_set_mat(const Mat_rm *const mat, Affine *const affine);       /* imutil.c:2620 */
 int init_tform(void *const tform, const tform_type type);                /* imutil.c:2540 */
+int init_Tps(Tps *tps, int dim, int terms);                              /* imutil.c:4213 (terms = N + dim + 1) */
+int resize_Tps(Tps *tps, int num_pts, int dim);                          /* imutil.c:4727 */
+extern const Tform_vtable Tps_vtable;                                    /* imutil.c:138; copy and write are functional here */
 void cleanup_tform(void *const tform);
 int copy_tform(const void *const src, void *const dst);
 size_t tform_get_size(const void *const tform);
@@ -585,6 +594,37 @@ int sift3d_amd_ransac_last_path(void);        /* 0 host, 1 device: the scoring p
 void sift3d_amd_set_ransac_profile(int on);
 double sift3d_amd_ransac_last_device_ms(void);
 
+/* ---- thin-plate-spline registration: fit from matches, warp on the device ----------------------------------------------------
+ * A Tps maps a point p of the reference volume to the source volume (the direction im_inv_transform needs):
+ *     f(p) = sum_n U(|p - c_n|^2) w_n + a_0 + a_x p_x + a_y p_y + a_z p_z,     U(r2) = r2 log r2, U(0) = 0,
+ * c_n the rows of kp_src, w_n and a_* the columns of params (Tps above).  apply_tform_xyz / apply_tform_Mat_rm evaluate it with
+ * the reference's expression and summation order (bit-identical to its apply_Tps_*); copy_tform deep-copies; write_tform writes
+ * one CSV of N + 4 rows x 6 columns: row n < N is [c_x c_y c_z w_x w_y w_z], the last four rows are [0 0 0 a_x a_y a_z] for the
+ * constant and the x, y, z coefficients.  im_inv_transform warps through a 3-D Tps on the device (s3d_k_inv_tps).
+ * init_tform(t, TPS) still fails as the reference's does: it has no point count to allocate with.  Use init_Tps(t, 3, 4).
+ *
+ * sift3d_amd_fit_tps: src, ref n x 3 doubles, one point per row (as find_tform_ransac takes them), f(ref_i) ~ src_i.  Solves
+ *     [K + lambda I, P; P^T, 0] [w; a] = [src; 0],   K_ij = U(|ref_i - ref_j|^2),  P = [1 x y z]
+ * in f64 by LU with partial pivoting; lambda = 0 interpolates, larger values trade fidelity for bending energy.  Rows whose ref
+ * point equals an earlier row's exactly are dropped with their src point.  Works in the coordinates given: with voxel
+ * coordinates of anisotropic volumes the bending energy is measured in voxels, not mm.  SIFT3D_FAILURE with
+ * sift3d_amd_last_error set for fewer than 4 remaining points, a singular system (coplanar points), lambda < 0 or NaN, and
+ * matrices of the wrong shape or type.  tps must have been initialised (init_Tps); it is resized. */
+int sift3d_amd_fit_tps(const Mat_rm *const src, const Mat_rm *const ref, double lambda, Tps *const tps);
+/* register_SIFT3D into `affine` (voxel space, as today), then a spline through the matches that agree with it:
+ * control points are the matches whose residual under the affine, in physical units and by find_tform_ransac's rule
+ * (!(e > thresh^2)), is within ctrl_thresh -- deliberately wider than the consensus threshold, which rejects exactly the matches
+ * that carry the deformation.  More than max_points of them: every k-th in match order, k = ceil(count / max_points).  They go
+ * to sift3d_amd_fit_tps in voxel coordinates.  opts NULL, or a field <= 0 (lambda < 0): the default of that field. */
+typedef struct {
+    double lambda;        /* default 1000 */
+    double ctrl_thresh;   /* default 4 * reg->ran.err_thresh */
+    int max_points;       /* default 512 */
+} sift3d_amd_tps_opts;
+#define SIFT3D_AMD_TPS_LAMBDA_DEFAULT 1000.0
+#define SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT 512
+int sift3d_amd_register_tps(Reg_SIFT3D *const reg, const sift3d_amd_tps_opts *const opts, Affine *const affine, Tps *const tps);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)
@@ -596,6 +636,7 @@ S3D_ABI_OFF(Image, xs, 72); S3D_ABI_OFF(Image, nc, 96); S3D_ABI_OFF(Image, cl_va
 S3D_ABI_SIZE(Reg_SIFT3D, 512); S3D_ABI_OFF(Reg_SIFT3D, sift3d, 48); S3D_ABI_OFF(Reg_SIFT3D, ran, 352);
 S3D_ABI_OFF(Reg_SIFT3D, desc_src, 368); S3D_ABI_OFF(Reg_SIFT3D, match_src, 432); S3D_ABI_OFF(Reg_SIFT3D, nn_thresh, 496);
 S3D_ABI_SIZE(Ransac, 16); S3D_ABI_SIZE(Tform, 16); S3D_ABI_SIZE(Affine, 48); S3D_ABI_OFF(Affine, A, 16); S3D_ABI_SIZE(Tform_vtable, 48);
+S3D_ABI_SIZE(Tps, 88); S3D_ABI_OFF(Tps, params, 16); S3D_ABI_OFF(Tps, kp_src, 48); S3D_ABI_OFF(Tps, dim, 80);
 S3D_ABI_SIZE(Mat_rm, 32); S3D_ABI_SIZE(Keypoint, 112); S3D_ABI_OFF(Keypoint, R, 40);
 S3D_ABI_OFF(Keypoint, xd, 72); S3D_ABI_OFF(Keypoint, sd, 96); S3D_ABI_OFF(Keypoint, o, 104);
 S3D_ABI_OFF(Keypoint, s, 108); S3D_ABI_SIZE(Slab, 24); S3D_ABI_SIZE(Keypoint_store, 48);

@@ -127,6 +127,16 @@ class Affine(C.Structure):
     _fields_ = [("tform", Tform), ("A", Mat_rm)]
 
 
+class Tps(C.Structure):
+    """Thin-plate spline: ``params`` dim x (N + dim + 1), ``kp_src`` N x dim (imtypes.h:380-385)."""
+    _fields_ = [("tform", Tform), ("params", Mat_rm), ("kp_src", Mat_rm), ("dim", C.c_int)]
+
+
+class TpsOpts(C.Structure):
+    """``sift3d_amd_tps_opts``; a field <= 0 (lambda < 0) takes its default."""
+    _fields_ = [("lambda_", C.c_double), ("ctrl_thresh", C.c_double), ("max_points", C.c_int)]
+
+
 class Reg_SIFT3D(C.Structure):
     _fields_ = [("src_units", C.c_double * 3), ("ref_units", C.c_double * 3), ("sift3d", SIFT3D), ("ran", Ransac),
                 ("desc_src", SIFT3D_Descriptor_store), ("desc_ref", SIFT3D_Descriptor_store), ("match_src", Mat_rm),
@@ -282,6 +292,7 @@ ABI_LAYOUT = [
     (Ransac, 16, {"num_iter": 8}),
     (Tform, 16, {"vtable": 8}),
     (Affine, 48, {"A": 16}),
+    (Tps, 88, {"params": 16, "kp_src": 48, "dim": 80}),
     (Reg_SIFT3D, 512, {"ref_units": 24, "sift3d": 48, "ran": 352, "desc_src": 368, "desc_ref": 400, "match_src": 432,
                        "match_ref": 464, "nn_thresh": 496, "verbose": 504}),
     (SIFT3D, 304, {"gss": 16, "gpyr": 80, "dog": 128, "im": 176, "peak_thresh": 280,

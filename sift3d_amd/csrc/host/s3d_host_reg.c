@@ -177,7 +177,7 @@ int init_tform(void *const tform, const tform_type type)
 
 tform_type tform_get_type(const void *const tform) { return ((const Tform *)tform)->type; }
 size_t tform_get_size(const void *const tform) { return ((const Tform *)tform)->vtable->get_size(); }
-size_t tform_type_get_size(const tform_type type) { return type == AFFINE ? sizeof(Affine) : 0; }
+size_t tform_type_get_size(const tform_type type) { return type == AFFINE ? sizeof(Affine) : type == TPS ? sizeof(Tps) : 0; }
 int copy_tform(const void *const src, void *const dst) { return ((const Tform *)src)->vtable->copy(src, dst); }
 int write_tform(const char *path, const void *const tform) { return ((const Tform *)tform)->vtable->write(path, tform); }
 void cleanup_tform(void *const tform)
@@ -342,6 +342,233 @@ static int s3d_solve_affine(const double *src, const double *ref, int npts, int 
     for (int r = 0; r < dim; r++)
         for (int c = 0; c < n; c++) A->u.data_double[r * n + c] = X[c * dim + r];
     return SIFT3D_SUCCESS;
+}
+
+/* ---- thin-plate spline (imtypes.h:380-385; imutil.c:2676-2805, 4213-4235, 4727-4744) ------------------------------------
+ * The reference has the struct, its allocation and the two apply functions; copy, write and the fit are this library's. */
+static int s3d_tps_is_3d(const Tps *const t)
+{
+    const int n = t->kp_src.num_rows;
+    return t->dim == IM_NDIMS && n >= 0 && t->kp_src.type == SIFT3D_DOUBLE && t->params.type == SIFT3D_DOUBLE &&
+           t->params.num_rows == IM_NDIMS && t->params.num_cols == n + IM_NDIMS + 1 && t->params.u.data_double != NULL &&
+           (n == 0 || (t->kp_src.num_cols == IM_NDIMS && t->kp_src.u.data_double != NULL));
+}
+
+/* the reference's expression and summation order; this file is compiled without contraction */
+static void s3d_apply_Tps_xyz(const void *const tps, const double x_in, const double y_in, const double z_in, double *const x_out,
+                              double *const y_out, double *const z_out)
+{
+    const Tps *const t = (const Tps *)tps;
+    const int n_ctrl = t->kp_src.num_rows;
+    const double *const c = t->kp_src.u.data_double, *const px = t->params.u.data_double, *const py = px + t->params.num_cols,
+                 *const pz = py + t->params.num_cols;
+    double temp_x = 0.0, temp_y = 0.0, temp_z = 0.0;
+    for (int n = 0; n < n_ctrl; n++) {
+        const double x_c = c[(size_t)n * 3], y_c = c[(size_t)n * 3 + 1], z_c = c[(size_t)n * 3 + 2];
+        const double r_sq = (x_in - x_c) * (x_in - x_c) + (y_in - y_c) * (y_in - y_c) + (z_in - z_c) * (z_in - z_c);
+        const double U = r_sq == 0 ? 0.0 : r_sq * log(r_sq);
+        temp_x += U * px[n];
+        temp_y += U * py[n];
+        temp_z += U * pz[n];
+    }
+    temp_x += px[n_ctrl]; temp_x += px[n_ctrl + 1] * x_in; temp_x += px[n_ctrl + 2] * y_in; temp_x += px[n_ctrl + 3] * z_in;
+    temp_y += py[n_ctrl]; temp_y += py[n_ctrl + 1] * x_in; temp_y += py[n_ctrl + 2] * y_in; temp_y += py[n_ctrl + 3] * z_in;
+    temp_z += pz[n_ctrl]; temp_z += pz[n_ctrl + 1] * x_in; temp_z += pz[n_ctrl + 2] * y_in; temp_z += pz[n_ctrl + 3] * z_in;
+    *x_out = temp_x; *y_out = temp_y; *z_out = temp_z;
+}
+
+/* in: 3 x num_pts, one point per COLUMN (the reference's format for this call); out likewise, resized here */
+static int s3d_apply_Tps_Mat_rm(const void *const tps, const Mat_rm *const in, Mat_rm *const out)
+{
+    const Tps *const t = (const Tps *)tps;
+    if (!s3d_tps_is_3d(t) || in->type != SIFT3D_DOUBLE || in->num_rows < IM_NDIMS) return SIFT3D_FAILURE;
+    const int num_pts = in->num_cols;
+    out->type = SIFT3D_DOUBLE;
+    out->num_rows = IM_NDIMS;
+    out->num_cols = num_pts;
+    if (resize_Mat_rm(out)) return SIFT3D_FAILURE;
+    for (int q = 0; q < num_pts; q++)
+        s3d_apply_Tps_xyz(tps, in->u.data_double[q], in->u.data_double[(size_t)num_pts + q],
+                          in->u.data_double[2 * (size_t)num_pts + q], out->u.data_double + q,
+                          out->u.data_double + (size_t)num_pts + q, out->u.data_double + 2 * (size_t)num_pts + q);
+    return SIFT3D_SUCCESS;
+}
+
+static int s3d_copy_Tps(const void *const src, void *const dst)
+{
+    const Tps *const s = (const Tps *)src;
+    Tps *const d = (Tps *)dst;
+    if (copy_Mat_rm(&s->params, &d->params) || copy_Mat_rm(&s->kp_src, &d->kp_src)) return SIFT3D_FAILURE;
+    d->dim = s->dim;
+    return SIFT3D_SUCCESS;
+}
+
+static size_t s3d_Tps_get_size(void) { return sizeof(Tps); }
+
+/* N + 4 rows x 6 columns: [c_x c_y c_z w_x w_y w_z] per control point, then [0 0 0 a_x a_y a_z] for the constant and the
+ * x, y, z coefficients */
+static int s3d_write_Tps(const char *path, const void *const tform)
+{
+    const Tps *const t = (const Tps *)tform;
+    Mat_rm m;
+    if (!s3d_tps_is_3d(t)) {
+        S3D_MSG("write_Tps: only 3-D splines can be written \n");
+        return SIFT3D_FAILURE;
+    }
+    const int n = t->kp_src.num_rows, cols = t->params.num_cols;
+    if (init_Mat_rm(&m, n + 4, 6, SIFT3D_DOUBLE, SIFT3D_TRUE)) return SIFT3D_FAILURE;
+    for (int i = 0; i < n + 4; i++)
+        for (int k = 0; k < 3; k++) {
+            if (i < n) m.u.data_double[(size_t)i * 6 + k] = t->kp_src.u.data_double[(size_t)i * 3 + k];
+            m.u.data_double[(size_t)i * 6 + 3 + k] = t->params.u.data_double[(size_t)k * cols + i];
+        }
+    const int rc = write_Mat_rm(path, &m);
+    cleanup_Mat_rm(&m);
+    return rc;
+}
+
+static void s3d_cleanup_Tps(void *const tps)
+{
+    cleanup_Mat_rm(&((Tps *)tps)->params);
+    cleanup_Mat_rm(&((Tps *)tps)->kp_src);
+}
+
+const Tform_vtable Tps_vtable = {s3d_copy_Tps, s3d_apply_Tps_xyz, s3d_apply_Tps_Mat_rm, s3d_Tps_get_size, s3d_write_Tps,
+                                 s3d_cleanup_Tps};
+
+int init_Tps(Tps *tps, int dim, int terms)
+{
+    if (dim < 2) return SIFT3D_FAILURE;
+    tps->tform.type = TPS;
+    tps->tform.vtable = &Tps_vtable;
+    if (init_Mat_rm(&tps->params, dim, terms, SIFT3D_DOUBLE, SIFT3D_TRUE)) return SIFT3D_FAILURE;
+    if (init_Mat_rm(&tps->kp_src, terms - dim - 1, dim, SIFT3D_DOUBLE, SIFT3D_TRUE)) return SIFT3D_FAILURE;
+    tps->dim = dim;
+    return SIFT3D_SUCCESS;
+}
+
+int resize_Tps(Tps *tps, int num_pts, int dim)
+{
+    tps->params.num_cols = num_pts + dim + 1;
+    tps->params.num_rows = dim;
+    tps->kp_src.num_rows = num_pts;
+    tps->kp_src.num_cols = dim;
+    if (resize_Mat_rm(&tps->params) || resize_Mat_rm(&tps->kp_src)) return SIFT3D_FAILURE;
+    tps->dim = dim;
+    return SIFT3D_SUCCESS;
+}
+
+/* 1 when the points (n x 3) span no volume: the 4 x 4 Gram matrix of [1 x y z], coordinates centred and scaled to [-1, 1],
+ * fails solve_Mat_rm's condition test (reciprocal condition below 100 eps).  With distinct points this is the only way the
+ * spline system is singular: r2 log r2 is conditionally positive definite of order 2. */
+static int s3d_tps_points_flat(const double *p, int n)
+{
+    double lo[3], hi[3], G[16], I4[16], X[16], scale = 0.0;
+    for (int k = 0; k < 3; k++) lo[k] = hi[k] = p[k];
+    for (int i = 1; i < n; i++)
+        for (int k = 0; k < 3; k++) {
+            const double v = p[(size_t)i * 3 + k];
+            if (v < lo[k]) lo[k] = v;
+            if (v > hi[k]) hi[k] = v;
+        }
+    for (int k = 0; k < 3; k++)
+        if (hi[k] - lo[k] > scale) scale = hi[k] - lo[k];
+    if (!(scale > 0.0) || !(scale <= DBL_MAX)) return 1;
+    memset(G, 0, sizeof(G));
+    memset(I4, 0, sizeof(I4));
+    for (int i = 0; i < n; i++) {
+        double q[4] = {1.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < 3; k++) q[k + 1] = (2.0 * p[(size_t)i * 3 + k] - (lo[k] + hi[k])) / scale;
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) G[a * 4 + b] += q[a] * q[b];
+    }
+    for (int a = 0; a < 4; a++) I4[a * 4 + a] = 1.0;
+    return s3d_solve_square(G, 4, I4, 4, X) != SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_fit_tps(const Mat_rm *const src, const Mat_rm *const ref, double lambda, Tps *const tps)
+{
+    if (src == NULL || ref == NULL || tps == NULL) {
+        s3d_api_set_error("sift3d_amd_fit_tps: NULL argument");
+        return SIFT3D_FAILURE;
+    }
+    if (src->type != SIFT3D_DOUBLE || ref->type != SIFT3D_DOUBLE) {
+        s3d_api_set_error("sift3d_amd_fit_tps: all matrices must have type double");
+        return SIFT3D_FAILURE;
+    }
+    if (src->num_cols != IM_NDIMS || ref->num_cols != IM_NDIMS || src->num_rows != ref->num_rows || src->num_rows < 0) {
+        s3d_api_set_error("sift3d_amd_fit_tps: src and ref must both be n x %d, one point per row. Provided: [%d x %d] and "
+                          "[%d x %d]", IM_NDIMS, src->num_rows, src->num_cols, ref->num_rows, ref->num_cols);
+        return SIFT3D_FAILURE;
+    }
+    if (!(lambda >= 0.0) || lambda > DBL_MAX) {
+        s3d_api_set_error("sift3d_amd_fit_tps: lambda must be a finite number >= 0. Provided: %f", lambda);
+        return SIFT3D_FAILURE;
+    }
+    const int nin = src->num_rows;
+    int rc = SIFT3D_FAILURE, n = 0;
+    double *R = (double *)malloc(sizeof(double) * 3 * (size_t)(nin + 1)), *S = (double *)malloc(sizeof(double) * 3 * (size_t)(nin + 1));
+    double *M = NULL, *B = NULL;
+    int *piv = NULL;
+    if (R == NULL || S == NULL) goto nomem;
+    for (int i = 0; i < nin; i++) {                        /* rows whose ref point equals an earlier row's are dropped */
+        const double *r = ref->u.data_double + (size_t)i * 3;
+        int dup = 0;
+        for (int j = 0; j < n && !dup; j++) dup = R[(size_t)j * 3] == r[0] && R[(size_t)j * 3 + 1] == r[1] && R[(size_t)j * 3 + 2] == r[2];
+        if (dup) continue;
+        memcpy(R + (size_t)n * 3, r, sizeof(double) * 3);
+        memcpy(S + (size_t)n * 3, src->u.data_double + (size_t)i * 3, sizeof(double) * 3);
+        n++;
+    }
+    if (n < IM_NDIMS + 1) {
+        s3d_api_set_error("sift3d_amd_fit_tps: a spline needs at least %d distinct points. Provided: %d (%d rows)", IM_NDIMS + 1, n, nin);
+        goto done;
+    }
+    if (s3d_tps_points_flat(R, n)) {
+        s3d_api_set_error("sift3d_amd_fit_tps: singular system: the %d reference points lie in one plane (or are not finite)", n);
+        goto done;
+    }
+    const int m = n + 4;
+    M = (double *)calloc((size_t)m * m, sizeof(double));
+    B = (double *)calloc((size_t)m * 3, sizeof(double));
+    piv = (int *)malloc(sizeof(int) * (size_t)m);
+    if (M == NULL || B == NULL || piv == NULL) goto nomem;
+    for (int i = 0; i < n; i++) {
+        const double *ri = R + (size_t)i * 3;
+        for (int j = 0; j < n; j++) {
+            const double *rj = R + (size_t)j * 3;
+            const double r_sq = (ri[0] - rj[0]) * (ri[0] - rj[0]) + (ri[1] - rj[1]) * (ri[1] - rj[1]) + (ri[2] - rj[2]) * (ri[2] - rj[2]);
+            M[(size_t)i * m + j] = r_sq == 0 ? 0.0 : r_sq * log(r_sq);
+        }
+        M[(size_t)i * m + i] += lambda;
+        M[(size_t)i * m + n] = M[(size_t)n * m + i] = 1.0;
+        for (int k = 0; k < 3; k++) {
+            M[(size_t)i * m + n + 1 + k] = M[(size_t)(n + 1 + k) * m + i] = ri[k];
+            B[(size_t)i * 3 + k] = S[(size_t)i * 3 + k];
+        }
+    }
+    int finite = s3d_lu(M, m, piv) == 0;
+    if (finite) {
+        s3d_lu_solve(M, piv, m, B, 3);
+        for (size_t i = 0; i < (size_t)m * 3; i++) finite &= B[i] - B[i] == 0.0;
+    }
+    if (!finite) {
+        s3d_api_set_error("sift3d_amd_fit_tps: singular system (%d points, lambda %g)", n, lambda);
+        goto done;
+    }
+    if (resize_Tps(tps, n, IM_NDIMS)) goto nomem;
+    tps->tform.type = TPS;
+    tps->tform.vtable = &Tps_vtable;
+    memcpy(tps->kp_src.u.data_double, R, sizeof(double) * 3 * (size_t)n);
+    for (int k = 0; k < 3; k++)
+        for (int j = 0; j < m; j++) tps->params.u.data_double[(size_t)k * m + j] = B[(size_t)j * 3 + k];
+    rc = SIFT3D_SUCCESS;
+    goto done;
+nomem:
+    s3d_api_set_error("sift3d_amd_fit_tps: out of memory (%d points)", nin);
+done:
+    free(R); free(S); free(M); free(B); free(piv);
+    return rc;
 }
 
 /* ---- RANSAC --------------------------------------------------------------------------------------- */
@@ -628,13 +855,15 @@ int im_inv_transform(const void *const tform, const Image *const src, const inte
         S3D_MSG("im_inv_transform: unrecognized interpolation type");
         return SIFT3D_FAILURE;
     }
-    if (tform_get_type(tform) != AFFINE || ((const Affine *)tform)->A.num_rows != IM_NDIMS) {
+    const int is_tps = tform_get_type(tform) == TPS && s3d_tps_is_3d((const Tps *)tform);
+    if (!is_tps && (tform_get_type(tform) != AFFINE || ((const Affine *)tform)->A.num_rows != IM_NDIMS)) {
         S3D_MSG("im_inv_transform: only 3-D affine transforms are supported \n");
         return SIFT3D_FAILURE;
     }
     if (dst->nc != src->nc || dst->data == NULL || src->data == NULL) return SIFT3D_FAILURE;
     const size_t ns = (size_t)src->nx * src->ny * src->nz * src->nc, nd = (size_t)dst->nx * dst->ny * dst->nz * dst->nc;
     float *d_src = NULL, *d_dst = NULL, *packed = NULL;
+    double *d_tps = NULL;                                   /* the spline: params (3 x (N + 4)), then kp_src (N x 3) */
     int rc = SIFT3D_FAILURE;
     /* the device works on default strides */
     const float *h_src = src->data;
@@ -644,15 +873,25 @@ int im_inv_transform(const void *const tform, const Image *const src, const inte
         h_src = packed;
     }
     if (!s3d_im_is_default_stride(dst)) im_default_stride(dst);
-    if (s3d_rt_malloc((void **)&d_src, ns * sizeof(float)) || s3d_rt_malloc((void **)&d_dst, nd * sizeof(float)) ||
-        s3d_rt_h2d(d_src, h_src, ns * sizeof(float), NULL) ||
-        s3d_k_inv_affine(d_src, src->nx, src->ny, src->nz, src->nc, d_dst, dst->nx, dst->ny, dst->nz,
-                         ((const Affine *)tform)->A.u.data_double, interp == LINEAR ? 0 : 1, NULL) ||
-        s3d_rt_d2h(dst->data, d_dst, nd * sizeof(float), NULL) || s3d_rt_sync(NULL))
+    int dev_rc = s3d_rt_malloc((void **)&d_src, ns * sizeof(float)) || s3d_rt_malloc((void **)&d_dst, nd * sizeof(float)) ||
+                 s3d_rt_h2d(d_src, h_src, ns * sizeof(float), NULL);
+    if (!dev_rc && is_tps) {
+        const Tps *const t = (const Tps *)tform;
+        const size_t n = (size_t)t->kp_src.num_rows, np = 3 * (n + 4);
+        dev_rc = s3d_rt_malloc((void **)&d_tps, (np + 3 * n) * sizeof(double)) ||
+                 s3d_rt_h2d(d_tps, t->params.u.data_double, np * sizeof(double), NULL) ||
+                 (n && s3d_rt_h2d(d_tps + np, t->kp_src.u.data_double, 3 * n * sizeof(double), NULL)) ||
+                 s3d_k_inv_tps(d_src, src->nx, src->ny, src->nz, src->nc, d_dst, dst->nx, dst->ny, dst->nz, d_tps + np, d_tps,
+                               (uint32_t)n, interp == LINEAR ? 0 : 1, NULL);
+    } else if (!dev_rc) {
+        dev_rc = s3d_k_inv_affine(d_src, src->nx, src->ny, src->nz, src->nc, d_dst, dst->nx, dst->ny, dst->nz,
+                                  ((const Affine *)tform)->A.u.data_double, interp == LINEAR ? 0 : 1, NULL);
+    }
+    if (dev_rc || s3d_rt_d2h(dst->data, d_dst, nd * sizeof(float), NULL) || s3d_rt_sync(NULL))
         S3D_MSG("im_inv_transform: device failure: %s\n", s3d_rt_last_error());
     else
         rc = SIFT3D_SUCCESS;
-    s3d_rt_free(d_src); s3d_rt_free(d_dst);
+    s3d_rt_free(d_src); s3d_rt_free(d_dst); s3d_rt_free(d_tps);
     free(packed);
     return rc;
 }
@@ -837,4 +1076,61 @@ int register_SIFT3D_resample(Reg_SIFT3D *const reg, const Image *const src, cons
 int get_matches_Reg_SIFT3D(const Reg_SIFT3D *const reg, Mat_rm *const match_src, Mat_rm *const match_ref)
 {
     return copy_Mat_rm(&reg->match_src, match_src) || copy_Mat_rm(&reg->match_ref, match_ref);
+}
+
+/* ---- affine, then a spline through the matches that agree with it (sift3d_amd.h) ------------------------------------------- */
+int sift3d_amd_register_tps(Reg_SIFT3D *const reg, const sift3d_amd_tps_opts *const opts, Affine *const affine, Tps *const tps)
+{
+    if (reg == NULL || affine == NULL || tps == NULL) {
+        s3d_api_set_error("sift3d_amd_register_tps: NULL argument");
+        return SIFT3D_FAILURE;
+    }
+    const double lambda = opts != NULL && opts->lambda >= 0.0 ? opts->lambda : SIFT3D_AMD_TPS_LAMBDA_DEFAULT;
+    const double thresh = opts != NULL && opts->ctrl_thresh > 0.0 ? opts->ctrl_thresh : 4.0 * reg->ran.err_thresh;
+    const int max_points = opts != NULL && opts->max_points > 0 ? opts->max_points : SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT;
+    if (opts != NULL && (opts->lambda != opts->lambda || opts->ctrl_thresh != opts->ctrl_thresh)) {
+        s3d_api_set_error("sift3d_amd_register_tps: lambda and ctrl_thresh must be numbers");
+        return SIFT3D_FAILURE;
+    }
+    if (tform_get_type(affine) != AFFINE || affine->A.num_rows != IM_NDIMS) {
+        s3d_api_set_error("sift3d_amd_register_tps: `affine` must be an initialised 3-D Affine");
+        return SIFT3D_FAILURE;
+    }
+    if (register_SIFT3D(reg, affine)) {
+        s3d_api_set_error("sift3d_amd_register_tps: the affine registration failed");
+        return SIFT3D_FAILURE;
+    }
+    /* the residual of a match in physical units: the voxel-space affine is the physical one with column j scaled by
+     * ref_units[j] and row i divided by src_units[i] (mm2im), so row i of the voxel residual times src_units[i] */
+    const int nm = reg->match_src.num_rows;
+    const double *const S = reg->match_src.u.data_double, *const R = reg->match_ref.u.data_double, *const A = affine->A.u.data_double;
+    const double thr2 = thresh * thresh;
+    int *keep = (int *)malloc(sizeof(int) * (size_t)(nm + 1)), count = 0, rc = SIFT3D_FAILURE;
+    Mat_rm ps, pr;
+    if (keep == NULL || init_Mat_rm(&ps, 0, IM_NDIMS, SIFT3D_DOUBLE, SIFT3D_FALSE)) { free(keep); return SIFT3D_FAILURE; }
+    if (init_Mat_rm(&pr, 0, IM_NDIMS, SIFT3D_DOUBLE, SIFT3D_FALSE)) { free(keep); cleanup_Mat_rm(&ps); return SIFT3D_FAILURE; }
+    for (int i = 0; i < nm; i++) {
+        const double *r = R + (size_t)i * IM_NDIMS, *s = S + (size_t)i * IM_NDIMS;
+        double e = 0.0;
+        for (int k = 0; k < IM_NDIMS; k++) {
+            const double d = (s[k] - (A[4 * k] * r[0] + A[4 * k + 1] * r[1] + A[4 * k + 2] * r[2] + A[4 * k + 3])) * reg->src_units[k];
+            e += d * d;
+        }
+        if (e > thr2) continue;
+        keep[count++] = i;
+    }
+    const int step = (count + max_points - 1) / max_points > 1 ? (count + max_points - 1) / max_points : 1;
+    const int n = (count + step - 1) / step;
+    ps.num_rows = pr.num_rows = n;
+    if (resize_Mat_rm(&ps) || resize_Mat_rm(&pr)) goto done;
+    for (int j = 0; j < n; j++) {
+        memcpy(ps.u.data_double + (size_t)j * IM_NDIMS, S + (size_t)keep[j * step] * IM_NDIMS, sizeof(double) * IM_NDIMS);
+        memcpy(pr.u.data_double + (size_t)j * IM_NDIMS, R + (size_t)keep[j * step] * IM_NDIMS, sizeof(double) * IM_NDIMS);
+    }
+    rc = sift3d_amd_fit_tps(&ps, &pr, lambda, tps);
+done:
+    free(keep);
+    cleanup_Mat_rm(&ps);
+    cleanup_Mat_rm(&pr);
+    return rc;
 }

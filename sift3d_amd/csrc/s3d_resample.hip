@@ -1,5 +1,6 @@
 /* s3d_resample.hip -- the device unit of the registration tail: the inverse affine warp of a
- * volume and, at the end of the file, the consensus counts of find_tform_ransac's hypotheses.
+ * volume, the inverse thin-plate-spline warp and, at the end of the file, the consensus counts of find_tform_ransac's
+ * hypotheses.
  *
  * im_inv_transform (imutil/imutil.c:2040-2085): every output voxel (x, y, z) is pushed through the
  * transform, (tx, ty, tz) = A [x y z 1]^T in f64 (apply_Affine_xyz, imutil.c:2651-2672), and the source
@@ -19,19 +20,12 @@ __device__ __forceinline__ double s3d_lanczos2(double x)
     return 2.0 * sin(pi_x) * sin(pi_x / 2.0) / (pi_x * pi_x);
 }
 
+/* The sample of src at (tx, ty, tz), every channel, to out[0 .. nc): the reference's resample_linear / resample_lanczos2.
+ * Shared by the affine and the spline warp. */
 template <int INTERP>
-__global__ void __launch_bounds__(256)
-k_inv_affine(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny,
-             int dnz, AffineD A)
+__device__ __forceinline__ void s3d_sample_store(const float *__restrict__ src, int snx, int sny, int snz, int nc,
+                                                 float *__restrict__ out, double tx, double ty, double tz)
 {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y = blockIdx.y, z = blockIdx.z;
-    if (x >= dnx) return;
-    const double xd = (double)x, yd = (double)y, zd = (double)z;
-    const double tx = A.a[0] * xd + A.a[1] * yd + A.a[2] * zd + A.a[3];
-    const double ty = A.a[4] * xd + A.a[5] * yd + A.a[6] * zd + A.a[7];
-    const double tz = A.a[8] * xd + A.a[9] * yd + A.a[10] * zd + A.a[11];
-    float *out = dst + (((size_t)z * dny + y) * dnx + x) * nc;
     const bool outside = tx < 0 || tx > snx - 1 || ty < 0 || ty > sny - 1 || tz < 0 || tz > snz - 1;
     const size_t sxs = (size_t)nc, sys = (size_t)nc * snx, szs = (size_t)nc * snx * sny;
     if (outside || !(tx == tx) || !(ty == ty) || !(tz == tz)) {
@@ -77,6 +71,22 @@ k_inv_affine(const float *__restrict__ src, int snx, int sny, int snz, int nc, f
     }
 }
 
+template <int INTERP>
+__global__ void __launch_bounds__(256)
+k_inv_affine(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny,
+             int dnz, AffineD A)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, z = blockIdx.z;
+    if (x >= dnx) return;
+    const double xd = (double)x, yd = (double)y, zd = (double)z;
+    const double tx = A.a[0] * xd + A.a[1] * yd + A.a[2] * zd + A.a[3];
+    const double ty = A.a[4] * xd + A.a[5] * yd + A.a[6] * zd + A.a[7];
+    const double tz = A.a[8] * xd + A.a[9] * yd + A.a[10] * zd + A.a[11];
+    float *out = dst + (((size_t)z * dny + y) * dnx + x) * nc;
+    s3d_sample_store<INTERP>(src, snx, sny, snz, nc, out, tx, ty, tz);
+}
+
 /* d_src: snx x sny x snz x nc (channels interleaved), d_dst: dnx x dny x dnz x nc; A: 3 x 4 row-major
  * doubles mapping output voxel coordinates to source voxel coordinates; interp 0 = linear, 1 = Lanczos-2. */
 extern "C" int s3d_k_inv_affine(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny,
@@ -93,6 +103,74 @@ extern "C" int s3d_k_inv_affine(const float *d_src, int snx, int sny, int snz, i
     else if (interp == 1)
         hipLaunchKernelGGL((k_inv_affine<1>), grid, dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, nc, d_dst, dnx,
                            dny, dnz, a);
+    else
+        S3D_FAIL("unrecognized interpolation type");
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* ---- inverse thin-plate-spline warp (im_inv_transform through apply_Tps_xyz, imutil.c:2676-2729) --------------------------
+ * One thread per output voxel, x-consecutive lanes as above.  Every voxel sums U(r2) = r2 log r2 over all control points in
+ * f64: the kernel is bound by the f64 log, not by memory.  A control point is six doubles (its coordinates and its three
+ * weights) that every lane of the workgroup needs at the same time: the workgroup stages S3D_TPS_TILE of them in LDS
+ * (6 KiB) and each lane reads them from there at one address (a broadcast, no bank conflict), so any n_ctrl streams through.
+ * Control points ascend; the sum uses fused multiply-adds (fewer roundings than the reference's, 5 f64 instructions less per
+ * point: 84 f64 VALU instructions per voxel and point in all, 73 of them the log; 104 VGPRs, no private segment; 256^3 x 512
+ * points in 22.6 ms, 82 % of the f64 issue rate, profiles/tps_warp_cost.txt); r2 == 0 is tested explicitly, since control points sit on voxels of the output grid and 0 * log(0) is NaN.  The
+ * tail -- the constant, then the x, y and z terms -- is the reference's expression, separately rounded (this file is compiled
+ * without contraction), so n_ctrl = 0 gives the reference's bits.  No lane leaves before the last barrier. */
+template <int INTERP>
+__global__ void __launch_bounds__(256)
+k_inv_tps(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny, int dnz,
+          const double *__restrict__ ctrl, const double *__restrict__ params, uint32_t n_ctrl)
+{
+    __shared__ double s_pt[S3D_TPS_TILE * 6];               /* per point: x y z w_x w_y w_z */
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, z = blockIdx.z;
+    const double xd = (double)x, yd = (double)y, zd = (double)z;
+    const size_t row = (size_t)n_ctrl + 4;                  /* row length of params */
+    double tx = 0.0, ty = 0.0, tz = 0.0;
+    for (uint32_t n0 = 0; n0 < n_ctrl; n0 += S3D_TPS_TILE) {
+        const uint32_t nt = n_ctrl - n0 < (uint32_t)S3D_TPS_TILE ? n_ctrl - n0 : (uint32_t)S3D_TPS_TILE;
+        if (n0) __syncthreads();                            /* the previous tile has been read by every lane */
+        for (uint32_t e = threadIdx.x; e < nt * 6u; e += 256u) {
+            const uint32_t j = e / 6u, k = e - j * 6u;
+            s_pt[e] = k < 3u ? ctrl[(size_t)(n0 + j) * 3 + k] : params[(size_t)(k - 3u) * row + n0 + j];
+        }
+        __syncthreads();
+        for (uint32_t j = 0; j < nt; j++) {
+            const double *p = s_pt + j * 6u;
+            const double dx = xd - p[0], dy = yd - p[1], dz = zd - p[2];
+            const double r2 = fma(dz, dz, fma(dy, dy, dx * dx));
+            const double u = r2 == 0.0 ? 0.0 : r2 * log(r2);
+            tx = fma(u, p[3], tx);
+            ty = fma(u, p[4], ty);
+            tz = fma(u, p[5], tz);
+        }
+    }
+    if (x >= dnx) return;
+    const double *ax = params + n_ctrl, *ay = ax + row, *az = ay + row;
+    tx += ax[0]; tx += ax[1] * xd; tx += ax[2] * yd; tx += ax[3] * zd;
+    ty += ay[0]; ty += ay[1] * xd; ty += ay[2] * yd; ty += ay[3] * zd;
+    tz += az[0]; tz += az[1] * xd; tz += az[2] * yd; tz += az[3] * zd;
+    float *out = dst + (((size_t)z * dny + y) * dnx + x) * nc;
+    s3d_sample_store<INTERP>(src, snx, sny, snz, nc, out, tx, ty, tz);
+}
+
+/* d_ctrl: n_ctrl x 3, d_params: 3 x (n_ctrl + 4), row-major doubles (the Tps struct's kp_src and params); the rest as above. */
+extern "C" int s3d_k_inv_tps(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny, int dnz,
+                             const double *d_ctrl, const double *d_params, uint32_t n_ctrl, int interp, s3d_stream stream)
+{
+    if (snx < 1 || sny < 1 || snz < 1 || nc < 1 || dnx < 1 || dny < 1 || dnz < 1) S3D_FAIL("bad dimensions");
+    if (dny > 65535 || dnz > 65535) S3D_FAIL("volume too large for the resampling grid");
+    if (d_params == NULL || (n_ctrl > 0 && d_ctrl == NULL)) S3D_FAIL("missing spline parameters");
+    const dim3 grid(s3d_div_up(dnx, 256), dny, dnz);
+    if (interp == 0)
+        hipLaunchKernelGGL((k_inv_tps<0>), grid, dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, nc, d_dst, dnx, dny,
+                           dnz, d_ctrl, d_params, n_ctrl);
+    else if (interp == 1)
+        hipLaunchKernelGGL((k_inv_tps<1>), grid, dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, nc, d_dst, dnx, dny,
+                           dnz, d_ctrl, d_params, n_ctrl);
     else
         S3D_FAIL("unrecognized interpolation type");
     S3D_CHECK_LAUNCH();

@@ -52,6 +52,11 @@ def bind_extensions(L: C.CDLL) -> None:
         L.sift3d_amd_set_subvoxel.argtypes = [P(abi.SIFT3D), C.c_int]
         L.sift3d_amd_get_subvoxel.argtypes = [P(abi.SIFT3D)]
         L.sift3d_amd_last_subvoxel_counts.argtypes = [P(abi.SIFT3D), P(C.c_long)]
+    if hasattr(L, "sift3d_amd_fit_tps"):                  # (absent from builds older than the thin-plate spline)
+        L.init_Tps.argtypes = [P(abi.Tps), C.c_int, C.c_int]
+        L.resize_Tps.argtypes = [P(abi.Tps), C.c_int, C.c_int]
+        L.sift3d_amd_fit_tps.argtypes = [P(abi.Mat_rm), P(abi.Mat_rm), C.c_double, P(abi.Tps)]
+        L.sift3d_amd_register_tps.argtypes = [P(abi.Reg_SIFT3D), P(abi.TpsOpts), P(abi.Affine), P(abi.Tps)]
 
 
 class DeviceLib:
@@ -107,6 +112,9 @@ class DeviceLib:
             L.s3d_k_ransac_count.argtypes = [_vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, _vp, _vp]
         if hasattr(L, "s3d_k_refine_keys"):               # (absent from builds older than the sub-voxel refinement)
             L.s3d_k_refine_keys.argtypes = [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]
+        if hasattr(L, "s3d_k_inv_tps"):                   # (absent from builds older than the thin-plate spline)
+            L.s3d_k_inv_tps.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                        C.c_uint32, C.c_int, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -228,6 +236,15 @@ class DeviceLib:
         d_src, d_ref npts x 3 and d_models nmodels x 12 doubles on the device."""
         self.check(self.L.s3d_k_ransac_count(_vp(d_src), _vp(d_ref), npts, _vp(d_models), nmodels, thr2, _vp(d_counts),
                                              _vp(stream)), "s3d_k_ransac_count")
+
+    # --- thin-plate-spline warp -----------------------------------------------------------------------------
+    def inv_tps(self, d_src: int, sdims, nc: int, d_dst: int, ddims, d_ctrl: int | None, d_params: int, n_ctrl: int,
+                interp: int = 0, stream=None) -> None:
+        """d_dst (ddims = (nx, ny, nz), nc channels, float32) = d_src (sdims) sampled at the spline of every output voxel
+        (s3d_k_inv_tps): d_ctrl n_ctrl x 3 and d_params 3 x (n_ctrl + 4) doubles on the device; interp 0 tri-linear,
+        1 Lanczos-2."""
+        self.check(self.L.s3d_k_inv_tps(_vp(d_src), sdims[0], sdims[1], sdims[2], nc, _vp(d_dst), ddims[0], ddims[1], ddims[2],
+                                        _vp(d_ctrl), _vp(d_params), n_ctrl, interp, _vp(stream)), "s3d_k_inv_tps")
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
