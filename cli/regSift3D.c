@@ -5,7 +5,8 @@
  *     regSift3D [SIFT3D options] [--matches m.csv] [--transform t.csv] [--warped w.nii] [--nn_thresh v]
  *               [--err_thresh v] [--num_iter n] [--type affine] [--resample] source.nii reference.nii
  * and, beyond the reference, [--tps] [--tps_lambda v] [--tps_thresh v] [--tps_max_points n]: a thin-plate spline fitted to
- * the matches near the affine map (sift3d_amd_register_tps), written by --transform and used by --warped,
+ * the matches near the affine map (sift3d_amd_register_tps), written by --transform and used by --warped, and
+ * [--metrics m.csv] [--metric_bins n]: the similarity of the images before and after (sift3d_amd_im_similarity),
  * linked against libsift3d_amd.so.  Detection, description, matching and the warp run as HIP kernels;
  * RANSAC is host C.  As in the reference, --err_thresh and --num_iter are parsed after the Ransac
  * parameters have been copied into the registration object, so they do not reach the estimator
@@ -60,6 +61,15 @@ static void usage(void)
            " --tps_max_points [value] - Largest number of control points. \n"
            "       (default: %d) \n"
            "\n"
+           "Similarity options: \n"
+           " --metrics [filename] - How well the images agree, one row per \n"
+           "       stage: before registration, under the affine fit and, \n"
+           "       with --tps, under the spline. Columns: n (voxels of the \n"
+           "       overlap), n_total, mse, mae, ncc, mi, nmi. \n"
+           "       Supported file formats: .csv, .csv.gz \n"
+           " --metric_bins [value] - Bins per axis of the joint histogram \n"
+           "       behind mi and nmi, in the interval [2, %d]. (default: %d) \n"
+           "\n"
            "Other options: \n"
            " --nn_thresh [value] - Matching threshold on the nearest neighbor \n"
            "       ratio, in the interval (0, 1]. (default: %.2f) \n"
@@ -74,7 +84,8 @@ static void usage(void)
            "	have very different resolutions, for example registering 5mm \n"
            "	to 1mm slices. \n"
            "\n",
-           SIFT3D_AMD_TPS_LAMBDA_DEFAULT, SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT, SIFT3D_nn_thresh_default,
+           SIFT3D_AMD_TPS_LAMBDA_DEFAULT, SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT, SIFT3D_AMD_SIMILARITY_BINS_MAX,
+           SIFT3D_AMD_SIMILARITY_BINS_DEFAULT, SIFT3D_nn_thresh_default,
            SIFT3D_err_thresh_default, SIFT3D_num_iter_default);
     print_opts_SIFT3D();
 }
@@ -100,7 +111,7 @@ static void complain_path(const char *what, const char *path)
 int main(int argc, char *argv[])
 {
     enum { MATCHES = 'a', TRANSFORM, WARPED, CONCAT, KEYS, LINES, NN_THRESH, ERR_THRESH, NUM_ITER, TYPE, RESAMPLE, TPS_FIT, TPS_LAMBDA,
-           TPS_THRESH, TPS_MAX_POINTS };
+           TPS_THRESH, TPS_MAX_POINTS, METRICS, METRIC_BINS };
     static const struct option longopts[] = {{"matches", required_argument, NULL, MATCHES},
                                              {"transform", required_argument, NULL, TRANSFORM},
                                              {"warped", required_argument, NULL, WARPED},
@@ -116,6 +127,8 @@ int main(int argc, char *argv[])
                                              {"tps_lambda", required_argument, NULL, TPS_LAMBDA},
                                              {"tps_thresh", required_argument, NULL, TPS_THRESH},
                                              {"tps_max_points", required_argument, NULL, TPS_MAX_POINTS},
+                                             {"metrics", required_argument, NULL, METRICS},
+                                             {"metric_bins", required_argument, NULL, METRIC_BINS},
                                              {0, 0, 0, 0}};
     Reg_SIFT3D reg;
     SIFT3D sift3d;
@@ -126,7 +139,8 @@ int main(int argc, char *argv[])
     Tps tps;
     sift3d_amd_tps_opts tps_opts = {-1.0, 0.0, 0};     /* the library's defaults */
     const char *match_path = NULL, *tform_path = NULL, *warped_path = NULL, *concat_path = NULL, *keys_path = NULL,
-               *lines_path = NULL;
+               *lines_path = NULL, *metrics_path = NULL;
+    sift3d_amd_similarity_opts sim_opts = {0, LINEAR, {0.0, 0.0}, {0.0, 0.0}};   /* the library's defaults */
     int have_match = 0, have_tform = 0, resample = 0, use_tps = 0;
 
     switch (parse_gnu(argc, argv)) {
@@ -189,6 +203,11 @@ int main(int argc, char *argv[])
             tps_opts.max_points = atoi(optarg);
             if (tps_opts.max_points < 4) { complain("Invalid value for tps_max_points."); return 1; }
             break;
+        case METRICS: metrics_path = optarg; have_tform = 1; break;
+        case METRIC_BINS:
+            sim_opts.bins = atoi(optarg);
+            if (sim_opts.bins < 2 || sim_opts.bins > SIFT3D_AMD_SIMILARITY_BINS_MAX) { complain("Invalid value for metric_bins."); return 1; }
+            break;
         default: return 1;
         }
     }
@@ -197,7 +216,8 @@ int main(int argc, char *argv[])
     if (argc - optind > 2) { complain("Too many arguments."); return 1; }
     const char *src_path = argv[optind], *ref_path = argv[optind + 1];
     if (use_tps && resample) { complain("--tps cannot be combined with --resample."); return 1; }
-    use_tps = use_tps && have_tform;                   /* the spline only shows in --transform and --warped */
+    if (metrics_path != NULL && resample) { complain("--metrics cannot be combined with --resample."); return 1; }
+    use_tps = use_tps && have_tform;                   /* the spline only shows in --transform, --warped and --metrics */
     if (init_tform(&tform, AFFINE) || init_Tps(&tps, IM_NDIMS, IM_NDIMS + 1)) return 1;
     if (im_read(src_path, &src)) { complain_path("Failed to read the source image", src_path); return 1; }
     if (im_read(ref_path, &ref)) { complain_path("Failed to read the reference image", ref_path); return 1; }
@@ -233,6 +253,24 @@ int main(int argc, char *argv[])
     if (tform_path != NULL && write_tform(tform_path, tform_out)) {
         complain_path("Failed to write the transformation parameters", tform_path);
         return 1;
+    }
+    if (metrics_path != NULL) {                        /* one row per stage, on the images as read */
+        const void *const stages[3] = {NULL, &tform, &tps};
+        const int nstages = use_tps ? 3 : 2;
+        Mat_rm metrics;
+        if (init_Mat_rm(&metrics, nstages, 7, SIFT3D_DOUBLE, SIFT3D_TRUE)) { complain_bug("Failed to allocate the metrics."); return 1; }
+        for (int i = 0; i < nstages; i++) {
+            sift3d_amd_similarity sim;
+            if (sift3d_amd_im_similarity(stages[i], &src, &ref, &sim_opts, &sim, NULL)) {
+                complain("Failed to compute the similarity of the images.");
+                return 1;
+            }
+            double *const row = metrics.u.data_double + (size_t)i * 7;
+            row[0] = (double)sim.n; row[1] = (double)sim.n_total; row[2] = sim.mse; row[3] = sim.mae; row[4] = sim.ncc;
+            row[5] = sim.mi; row[6] = sim.nmi;
+        }
+        if (write_Mat_rm(metrics_path, &metrics)) { complain_path("Failed to write the metrics", metrics_path); return 1; }
+        cleanup_Mat_rm(&metrics);
     }
     if (warped_path != NULL) {
         Image warped;

@@ -445,6 +445,38 @@ int s3d_k_inv_tps(const float *d_src, int snx, int sny, int snz, int nc, float *
 int s3d_k_ransac_count(const double *d_src, const double *d_ref, uint32_t npts, const double *d_models, uint32_t nmodels,
                        double thr2, int *d_counts, s3d_stream stream);
 
+/* ---- similarity of a source under a transform against a reference (s3d_resample.hip; extension, sift3d_amd_im_similarity) ----
+ * One pass over the reference volume d_ref (rnx x rny x rnz, one channel): voxel (x, y, z) goes through the transform exactly
+ * as in s3d_k_inv_affine / s3d_k_inv_tps (the kernels share the coordinate and sampling functions), the one-channel source
+ * d_src is sampled there, and the pair (a, b) = (reference voxel, the float the warp would have stored) is accumulated instead
+ * of stored.  A voxel counts iff the warp would sample it (no coordinate outside [0, n - 1], none NaN) and a and b are finite.
+ *   d_hist[ia * bins + ib] (u64, bins^2, zeroed by the call): ia = bin of a, t = ((double)a - ref_lo) * ref_scale in f64,
+ *       ia = t < 0 ? 0 : t >= bins ? bins - 1 : (int)t; ib likewise from b, src_lo, src_scale.  Integer atomics: exact.
+ *   d_sums[0 .. 7): sum a', sum b', sum a'^2, sum b'^2, sum a'b', sum (a - b)^2, sum |a - b| in f64, a' = a - c_ref,
+ *       b' = b - c_src.  No floating-point atomics: per-workgroup partials in d_scratch, added by a second launch in a fixed
+ *       order; which voxels a thread sums depends on the dimensions and bins only, so a call's bits repeat.
+ * bins in 2 .. S3D_SIM_MAX_BINS; interp as for the warps.  d_scratch: s3d_k_similarity_scratch_bytes(..) bytes (0: bad
+ * arguments), owned by the call until it has run.  Fails with a message for volumes whose rows (rny * rnz) exceed 2^31 - 1 or
+ * whose share per workgroup would overflow a 32-bit counter. */
+#define S3D_SIM_MAX_BINS 128
+size_t s3d_k_similarity_scratch_bytes(int rnx, int rny, int rnz, int bins);
+int s3d_k_similarity_affine(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                            const double A[12], int interp, int bins, double ref_lo, double ref_scale, double src_lo,
+                            double src_scale, double c_ref, double c_src, unsigned long long *d_hist, double *d_sums,
+                            void *d_scratch, s3d_stream stream);
+int s3d_k_similarity_tps(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                         const double *d_ctrl, const double *d_params, uint32_t n_ctrl, int interp, int bins, double ref_lo,
+                         double ref_scale, double src_lo, double src_scale, double c_ref, double c_src,
+                         unsigned long long *d_hist, double *d_sums, void *d_scratch, s3d_stream stream);
+/* Profiling knob of the calling thread: 1 -- lanes of a wave that share the first counted lane's histogram counter add their
+ * number with one LDS atomic (volumes whose voxels crowd into one background bin); 0 -- every lane its own atomic; < 0 -- the
+ * default (0: profiles/similarity_cost.txt).  The histogram and the sums are the same either way. */
+void s3d_k_similarity_set_aggregate(int on);
+int s3d_k_similarity_get_aggregate(void);
+/* d_minmax[0], [1] = the minimum and maximum over the finite elements of d_v[0 .. n); both NaN when none is finite.
+ * Integer maxima over an order-preserving encoding: the result does not depend on the schedule. */
+int s3d_k_minmax_finite(const float *d_v, size_t n, float *d_minmax, s3d_stream stream);
+
 /* ---- matcher (s3d_match.hip; replaces match_desc, sift.c:2892-2969) ------------------------------- */
 /* For each of the `na` query rows (row r = d_a + (d_a_sel ? d_a_sel[r] : r) * a_stride, 768 floats) the
  * smallest and second-smallest f64 sum of squared differences over the nb rows of d_b and the index of

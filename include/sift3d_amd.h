@@ -625,6 +625,47 @@ typedef struct {
 #define SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT 512
 int sift3d_amd_register_tps(Reg_SIFT3D *const reg, const sift3d_amd_tps_opts *const opts, Affine *const affine, Tps *const tps);
 
+/* ---- similarity of a registration: MSE, NCC and mutual information on the device ------------------------------------------
+ * "How well does src under tform agree with ref?"  One fused pass over the reference volume (s3d_k_similarity_*): every voxel
+ * (x, y, z) of ref goes through tform exactly as im_inv_transform pushes it (a 3-D Affine, a 3-D Tps, or NULL: the identity,
+ * scored as the affine [I | 0]), src is sampled there (LINEAR or LANCZOS2), and the pair a = ref voxel, b = the float the warp
+ * would have stored is accumulated; the warped volume is never written.  Single-channel volumes only.
+ *   Overlap: the voxels the warp samples (no coordinate outside [0, n - 1] of src, none NaN) whose a and b are both finite.
+ *       Everything below is over the overlap; n is its size, n_total the voxels of ref.
+ *   Joint histogram: bins B in 2 .. 128 over [ref_range] x [src_range]; the bin of a is t = ((double)a - lo) * (B / (hi - lo))
+ *       in f64, each operation rounded, index t < 0 ? 0 : t >= B ? B - 1 : (int)t (so a == hi lands in bin B - 1 and Lanczos
+ *       overshoot clamps); an empty range (hi == lo) has scale 0: everything in bin 0.  joint[ia * B + ib], row = reference
+ *       bin, 64-bit counts; n is their sum.  Exact whatever the schedule.
+ *   Default ranges: the minimum and maximum over the finite voxels of each whole volume (src itself, not its warp), found on
+ *       the device; a volume without a finite voxel fails.  A caller's range is used when its [1] > [0].
+ *   Moments: seven f64 sums about the pivots c = 0.5 * (lo + hi) of the two ranges; from them, in f64,
+ *       mean = c + S/n, var = S2/n - (S/n)^2, cov = Sab/n - (Sa/n)(Sb/n), ncc = cov / sqrt(var_ref * var_src) (NaN when a
+ *       variance is <= 0), mse = sum (a - b)^2 / n, mae = sum |a - b| / n.  The sums are added in a fixed order: two calls on
+ *       the same device and build return the same bits.
+ *   Entropies in nats from the histogram's marginals and cells; mi = h_ref + h_src - h_joint; nmi = (h_ref + h_src) / h_joint
+ *       (NaN when h_joint == 0).
+ *   n == 0 is a success: n = 0 and every statistic NaN.
+ * SIFT3D_FAILURE with sift3d_amd_last_error set, and out / joint untouched, for: bins outside 2 .. 128 (0: 64), an interp that
+ * is neither LINEAR nor LANCZOS2, a tform that is neither NULL, a 3-D Affine nor a 3-D Tps, nc != 1, NULL data, a NaN in a
+ * range, a volume without a finite voxel, and a device failure.  opts NULL: all defaults. */
+typedef struct { long long n, n_total; double mean_ref, mean_src, var_ref, var_src, mse, mae, ncc,
+                 h_ref, h_src, h_joint, mi, nmi; } sift3d_amd_similarity;
+typedef struct { int bins;              /* 0: 64 */
+                 interp_type interp;    /* LINEAR */
+                 double ref_range[2], src_range[2];   /* used when [1] > [0], else the volume's finite min / max */
+               } sift3d_amd_similarity_opts;
+#define SIFT3D_AMD_SIMILARITY_BINS_DEFAULT 64
+#define SIFT3D_AMD_SIMILARITY_BINS_MAX 128
+/* Host volumes: non-default strides are gathered as im_inv_transform does, both volumes are uploaded, scored and freed. */
+int sift3d_amd_im_similarity(const void *tform, const Image *src, const Image *ref,
+                             const sift3d_amd_similarity_opts *opts, sift3d_amd_similarity *out,
+                             unsigned long long *joint /* bins*bins, row = reference bin; may be NULL */);
+/* Device-resident volumes (x fastest, default strides); the work is ordered on hip_stream and has completed on return. */
+int sift3d_amd_similarity_dev(const void *tform, const float *d_src, int snx, int sny, int snz,
+                              const float *d_ref, int rnx, int rny, int rnz,
+                              const sift3d_amd_similarity_opts *opts, sift3d_amd_similarity *out,
+                              unsigned long long *joint, void *hip_stream);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

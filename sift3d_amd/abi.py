@@ -137,6 +137,18 @@ class TpsOpts(C.Structure):
     _fields_ = [("lambda_", C.c_double), ("ctrl_thresh", C.c_double), ("max_points", C.c_int)]
 
 
+class Similarity(C.Structure):
+    """``sift3d_amd_similarity``: the scores of a source under a transform against a reference, over their overlap."""
+    _fields_ = [("n", C.c_longlong), ("n_total", C.c_longlong)] + \
+               [(f, C.c_double) for f in ("mean_ref", "mean_src", "var_ref", "var_src", "mse", "mae", "ncc", "h_ref", "h_src",
+                                          "h_joint", "mi", "nmi")]
+
+
+class SimilarityOpts(C.Structure):
+    """``sift3d_amd_similarity_opts``; bins 0: 64, interp 0 tri-linear / 1 Lanczos-2, a range is used when [1] > [0]."""
+    _fields_ = [("bins", C.c_int), ("interp", C.c_int), ("ref_range", C.c_double * 2), ("src_range", C.c_double * 2)]
+
+
 class Reg_SIFT3D(C.Structure):
     _fields_ = [("src_units", C.c_double * 3), ("ref_units", C.c_double * 3), ("sift3d", SIFT3D), ("ran", Ransac),
                 ("desc_src", SIFT3D_Descriptor_store), ("desc_ref", SIFT3D_Descriptor_store), ("match_src", Mat_rm),

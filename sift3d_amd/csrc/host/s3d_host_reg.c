@@ -1134,3 +1134,201 @@ done:
     cleanup_Mat_rm(&pr);
     return rc;
 }
+
+/* ---- similarity of a registration: MSE, NCC and mutual information (sift3d_amd.h) ------------------------------------------
+ * The device accumulates the joint histogram and seven f64 sums (s3d_k_similarity_*); everything derived from them is here. */
+static double s3d_entropy_nats(const double *const counts, const size_t num, const double n)
+{
+    double h = 0.0;
+    for (size_t i = 0; i < num; i++)
+        if (counts[i] > 0.0) {
+            const double p = counts[i] / n;
+            h -= p * log(p);
+        }
+    return h;
+}
+
+static void s3d_similarity_derive(const unsigned long long *const hist, const int bins, const double *const S,
+                                  const double c_ref, const double c_src, const long long n_total, sift3d_amd_similarity *const out,
+                                  double *const marg /* 2 * bins */)
+{
+    const size_t nb2 = (size_t)bins * bins;
+    unsigned long long cnt = 0;
+    for (size_t i = 0; i < nb2; i++) cnt += hist[i];
+    out->n = (long long)cnt;
+    out->n_total = n_total;
+    if (cnt == 0) {
+        out->mean_ref = out->mean_src = out->var_ref = out->var_src = out->mse = out->mae = out->ncc = out->h_ref = out->h_src =
+            out->h_joint = out->mi = out->nmi = NAN;
+        return;
+    }
+    const double n = (double)cnt, ma = S[0] / n, mb = S[1] / n;
+    out->mean_ref = c_ref + ma;
+    out->mean_src = c_src + mb;
+    out->var_ref = S[2] / n - ma * ma;
+    out->var_src = S[3] / n - mb * mb;
+    const double cov = S[4] / n - ma * mb;
+    out->ncc = out->var_ref > 0.0 && out->var_src > 0.0 ? cov / sqrt(out->var_ref * out->var_src) : NAN;
+    out->mse = S[5] / n;
+    out->mae = S[6] / n;
+    double *const pa = marg, *const pb = marg + bins, hj = 0.0;
+    for (int i = 0; i < 2 * bins; i++) marg[i] = 0.0;
+    for (int i = 0; i < bins; i++)
+        for (int j = 0; j < bins; j++) {
+            const double c = (double)hist[(size_t)i * bins + j];
+            if (c > 0.0) {
+                const double p = c / n;
+                hj -= p * log(p);
+                pa[i] += c;                                /* integers below 2^53: exact */
+                pb[j] += c;
+            }
+        }
+    out->h_ref = s3d_entropy_nats(pa, (size_t)bins, n);
+    out->h_src = s3d_entropy_nats(pb, (size_t)bins, n);
+    out->h_joint = hj;
+    out->mi = out->h_ref + out->h_src - hj;
+    out->nmi = hj == 0.0 ? NAN : (out->h_ref + out->h_src) / hj;
+}
+
+#define S3D_SIM_FAIL(...) do { s3d_api_set_error("sift3d_amd_im_similarity: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+
+/* what both entry points refuse before anything is allocated; *bins and *interp receive the effective values */
+static int s3d_similarity_check(const void *const tform, const sift3d_amd_similarity_opts *const opts,
+                                const sift3d_amd_similarity *const out, int *const bins, int *const interp, int *const is_tps)
+{
+    if (out == NULL) S3D_SIM_FAIL("NULL result");
+    *bins = opts != NULL && opts->bins != 0 ? opts->bins : SIFT3D_AMD_SIMILARITY_BINS_DEFAULT;
+    if (*bins < 2 || *bins > SIFT3D_AMD_SIMILARITY_BINS_MAX) S3D_SIM_FAIL("bins must be in 2 .. 128 (0: 64), not %d", *bins);
+    *interp = opts != NULL ? (int)opts->interp : (int)LINEAR;
+    if (*interp != (int)LINEAR && *interp != (int)LANCZOS2) S3D_SIM_FAIL("unrecognized interpolation type %d", *interp);
+    *is_tps = 0;
+    if (tform != NULL) {
+        *is_tps = tform_get_type(tform) == TPS && s3d_tps_is_3d((const Tps *)tform);
+        if (!*is_tps && (tform_get_type(tform) != AFFINE || ((const Affine *)tform)->A.num_rows != IM_NDIMS ||
+                         ((const Affine *)tform)->A.num_cols != IM_NDIMS + 1 || ((const Affine *)tform)->A.type != SIFT3D_DOUBLE ||
+                         ((const Affine *)tform)->A.u.data_double == NULL))
+            S3D_SIM_FAIL("the transform must be NULL, a 3-D Affine or a 3-D Tps");
+    }
+    if (opts != NULL)
+        for (int i = 0; i < 2; i++)
+            if (opts->ref_range[i] != opts->ref_range[i] || opts->src_range[i] != opts->src_range[i])
+                S3D_SIM_FAIL("a range holds a NaN");
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_similarity_dev(const void *tform, const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny,
+                              int rnz, const sift3d_amd_similarity_opts *opts, sift3d_amd_similarity *out,
+                              unsigned long long *joint, void *hip_stream)
+{
+    int bins, interp, is_tps;
+    if (s3d_similarity_check(tform, opts, out, &bins, &interp, &is_tps)) return SIFT3D_FAILURE;
+    if (d_src == NULL || d_ref == NULL) S3D_SIM_FAIL("NULL data");
+    if (snx < 1 || sny < 1 || snz < 1 || rnx < 1 || rny < 1 || rnz < 1) S3D_SIM_FAIL("bad dimensions");
+    const size_t nb2 = (size_t)bins * bins, scratch_bytes = s3d_k_similarity_scratch_bytes(rnx, rny, rnz, bins);
+    const size_t ns = (size_t)snx * sny * snz, nr = (size_t)rnx * rny * rnz;
+    /* one device block: the histogram, the sums, two min / max pairs, the partials, the spline */
+    const Tps *const t = is_tps ? (const Tps *)tform : NULL;
+    const size_t nctrl = t ? (size_t)t->kp_src.num_rows : 0, np = t ? 3 * (nctrl + 4) : 0;
+    const size_t off_sums = nb2 * 8, off_mm = off_sums + 7 * 8, off_scr = off_mm + 16, off_tps = off_scr + scratch_bytes;
+    unsigned char *d_blk = NULL;
+    unsigned long long *h_hist = (unsigned long long *)malloc(nb2 * sizeof(*h_hist));
+    double *marg = (double *)malloc(2 * (size_t)bins * sizeof(double));
+    int rc = SIFT3D_FAILURE;
+    if (h_hist == NULL || marg == NULL) { s3d_api_set_error("sift3d_amd_im_similarity: out of memory"); goto done; }
+    if (s3d_rt_malloc((void **)&d_blk, off_tps + (np + 3 * nctrl) * sizeof(double))) goto dev_failed;
+    /* the ranges: the caller's where [1] > [0], else the finite minimum and maximum of the whole volume */
+    double rng[2][2];
+    const int have_ref = opts != NULL && opts->ref_range[1] > opts->ref_range[0];
+    const int have_src = opts != NULL && opts->src_range[1] > opts->src_range[0];
+    if (have_ref) { rng[0][0] = opts->ref_range[0]; rng[0][1] = opts->ref_range[1]; }
+    if (have_src) { rng[1][0] = opts->src_range[0]; rng[1][1] = opts->src_range[1]; }
+    if (!have_ref || !have_src) {
+        float mm[4];
+        float *const d_mm = (float *)(d_blk + off_mm);
+        if ((!have_ref && s3d_k_minmax_finite(d_ref, nr, d_mm, hip_stream)) ||
+            (!have_src && s3d_k_minmax_finite(d_src, ns, d_mm + 2, hip_stream)) ||
+            s3d_rt_d2h(mm, d_mm, sizeof(mm), hip_stream) || s3d_rt_sync(hip_stream))
+            goto dev_failed;
+        if (!have_ref) {
+            if (mm[0] != mm[0]) { s3d_api_set_error("sift3d_amd_im_similarity: the reference volume has no finite voxel"); goto done; }
+            rng[0][0] = mm[0]; rng[0][1] = mm[1];
+        }
+        if (!have_src) {
+            if (mm[2] != mm[2]) { s3d_api_set_error("sift3d_amd_im_similarity: the source volume has no finite voxel"); goto done; }
+            rng[1][0] = mm[2]; rng[1][1] = mm[3];
+        }
+    }
+    double scale[2], piv[2];
+    for (int k = 0; k < 2; k++) {
+        scale[k] = rng[k][1] > rng[k][0] ? (double)bins / (rng[k][1] - rng[k][0]) : 0.0;
+        piv[k] = 0.5 * (rng[k][0] + rng[k][1]);
+        if (!(fabs(scale[k]) <= DBL_MAX) || !(fabs(piv[k]) <= DBL_MAX)) {
+            s3d_api_set_error("sift3d_amd_im_similarity: a range is too narrow or too wide for %d bins", bins);
+            goto done;
+        }
+    }
+    unsigned long long *const d_hist = (unsigned long long *)d_blk;
+    double *const d_sums = (double *)(d_blk + off_sums);
+    void *const d_scr = d_blk + off_scr;
+    int dev_rc;
+    if (t != NULL) {
+        double *const d_tps = (double *)(d_blk + off_tps);
+        dev_rc = s3d_rt_h2d(d_tps, t->params.u.data_double, np * sizeof(double), hip_stream) ||
+                 (nctrl && s3d_rt_h2d(d_tps + np, t->kp_src.u.data_double, 3 * nctrl * sizeof(double), hip_stream)) ||
+                 s3d_k_similarity_tps(d_src, snx, sny, snz, d_ref, rnx, rny, rnz, d_tps + np, d_tps, (uint32_t)nctrl, interp == (int)LINEAR ? 0 : 1,
+                                      bins, rng[0][0], scale[0], rng[1][0], scale[1], piv[0], piv[1], d_hist, d_sums, d_scr, hip_stream);
+    } else {
+        static const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        const double *const A = tform != NULL ? ((const Affine *)tform)->A.u.data_double : identity;
+        dev_rc = s3d_k_similarity_affine(d_src, snx, sny, snz, d_ref, rnx, rny, rnz, A, interp == (int)LINEAR ? 0 : 1, bins, rng[0][0],
+                                         scale[0], rng[1][0], scale[1], piv[0], piv[1], d_hist, d_sums, d_scr, hip_stream);
+    }
+    double sums[7];
+    if (dev_rc || s3d_rt_d2h(h_hist, d_hist, nb2 * sizeof(*h_hist), hip_stream) || s3d_rt_d2h(sums, d_sums, sizeof(sums), hip_stream) ||
+        s3d_rt_sync(hip_stream))
+        goto dev_failed;
+    sift3d_amd_similarity res;
+    s3d_similarity_derive(h_hist, bins, sums, piv[0], piv[1], (long long)nr, &res, marg);
+    *out = res;
+    if (joint != NULL) memcpy(joint, h_hist, nb2 * sizeof(*h_hist));
+    rc = SIFT3D_SUCCESS;
+    goto done;
+dev_failed:
+    s3d_api_set_error("sift3d_amd_im_similarity: device failure: %s", s3d_rt_last_error());
+done:
+    s3d_rt_free(d_blk);
+    free(h_hist); free(marg);
+    return rc;
+}
+
+int sift3d_amd_im_similarity(const void *tform, const Image *src, const Image *ref, const sift3d_amd_similarity_opts *opts,
+                             sift3d_amd_similarity *out, unsigned long long *joint)
+{
+    int bins, interp, is_tps;
+    if (s3d_similarity_check(tform, opts, out, &bins, &interp, &is_tps)) return SIFT3D_FAILURE;
+    if (src == NULL || ref == NULL) S3D_SIM_FAIL("NULL image");
+    if (src->nc != 1 || ref->nc != 1) S3D_SIM_FAIL("single-channel volumes only (nc = %d and %d)", src->nc, ref->nc);
+    if (src->data == NULL || ref->data == NULL) S3D_SIM_FAIL("NULL data");
+    if (src->nx < 1 || src->ny < 1 || src->nz < 1 || ref->nx < 1 || ref->ny < 1 || ref->nz < 1) S3D_SIM_FAIL("bad dimensions");
+    const Image *const ims[2] = {src, ref};
+    float *d_im[2] = {NULL, NULL};
+    int rc = SIFT3D_FAILURE;
+    for (int k = 0; k < 2; k++) {                           /* the device works on default strides */
+        const size_t n = (size_t)ims[k]->nx * ims[k]->ny * ims[k]->nz;
+        const float *h = ims[k]->data;
+        float *packed = NULL;
+        if (!s3d_im_is_default_stride(ims[k])) {
+            if ((packed = (float *)malloc(n * sizeof(float))) == NULL) { s3d_api_set_error("sift3d_amd_im_similarity: out of memory"); goto done; }
+            s3d_im_gather(ims[k], packed);
+            h = packed;
+        }
+        const int dev_rc = s3d_rt_malloc((void **)&d_im[k], n * sizeof(float)) || s3d_rt_h2d(d_im[k], h, n * sizeof(float), NULL) ||
+                           s3d_rt_sync(NULL);
+        free(packed);
+        if (dev_rc) { s3d_api_set_error("sift3d_amd_im_similarity: device failure: %s", s3d_rt_last_error()); goto done; }
+    }
+    rc = sift3d_amd_similarity_dev(tform, d_im[0], src->nx, src->ny, src->nz, d_im[1], ref->nx, ref->ny, ref->nz, opts, out, joint, NULL);
+done:
+    s3d_rt_free(d_im[0]); s3d_rt_free(d_im[1]);
+    return rc;
+}

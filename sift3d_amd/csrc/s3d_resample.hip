@@ -1,6 +1,6 @@
 /* s3d_resample.hip -- the device unit of the registration tail: the inverse affine warp of a
- * volume, the inverse thin-plate-spline warp and, at the end of the file, the consensus counts of find_tform_ransac's
- * hypotheses.
+ * volume, the inverse thin-plate-spline warp, the consensus counts of find_tform_ransac's hypotheses and, at the end of the
+ * file, the similarity scores of a registration (the warp's pass that accumulates instead of storing).
  *
  * im_inv_transform (imutil/imutil.c:2040-2085): every output voxel (x, y, z) is pushed through the
  * transform, (tx, ty, tz) = A [x y z 1]^T in f64 (apply_Affine_xyz, imutil.c:2651-2672), and the source
@@ -20,16 +20,22 @@ __device__ __forceinline__ double s3d_lanczos2(double x)
     return 2.0 * sin(pi_x) * sin(pi_x / 2.0) / (pi_x * pi_x);
 }
 
+/* Whether s3d_sample_store samples at (tx, ty, tz): not outside [0, n - 1] on any axis and no NaN coordinate (NaN coordinates
+ * fail every comparison in the reference and would index out of range there). */
+__device__ __forceinline__ bool s3d_sample_inside(int snx, int sny, int snz, double tx, double ty, double tz)
+{
+    const bool outside = tx < 0 || tx > snx - 1 || ty < 0 || ty > sny - 1 || tz < 0 || tz > snz - 1;
+    return !(outside || !(tx == tx) || !(ty == ty) || !(tz == tz));
+}
+
 /* The sample of src at (tx, ty, tz), every channel, to out[0 .. nc): the reference's resample_linear / resample_lanczos2.
- * Shared by the affine and the spline warp. */
+ * Shared by the affine and the spline warp and by the similarity kernels. */
 template <int INTERP>
 __device__ __forceinline__ void s3d_sample_store(const float *__restrict__ src, int snx, int sny, int snz, int nc,
                                                  float *__restrict__ out, double tx, double ty, double tz)
 {
-    const bool outside = tx < 0 || tx > snx - 1 || ty < 0 || ty > sny - 1 || tz < 0 || tz > snz - 1;
     const size_t sxs = (size_t)nc, sys = (size_t)nc * snx, szs = (size_t)nc * snx * sny;
-    if (outside || !(tx == tx) || !(ty == ty) || !(tz == tz)) {
-        /* NaN coordinates fail every comparison in the reference and would index out of range there */
+    if (!s3d_sample_inside(snx, sny, snz, tx, ty, tz)) {
         for (int c = 0; c < nc; c++) out[c] = 0.0f;
         return;
     }
@@ -71,6 +77,15 @@ __device__ __forceinline__ void s3d_sample_store(const float *__restrict__ src, 
     }
 }
 
+/* (tx, ty, tz) = A [x y z 1]^T, left to right, every operation rounded (apply_Affine_xyz); shared by the affine warp and the
+ * affine similarity kernel, so both see the same bits */
+__device__ __forceinline__ void s3d_affine_xyz(const AffineD &A, double xd, double yd, double zd, double &tx, double &ty, double &tz)
+{
+    tx = A.a[0] * xd + A.a[1] * yd + A.a[2] * zd + A.a[3];
+    ty = A.a[4] * xd + A.a[5] * yd + A.a[6] * zd + A.a[7];
+    tz = A.a[8] * xd + A.a[9] * yd + A.a[10] * zd + A.a[11];
+}
+
 template <int INTERP>
 __global__ void __launch_bounds__(256)
 k_inv_affine(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny,
@@ -80,9 +95,8 @@ k_inv_affine(const float *__restrict__ src, int snx, int sny, int snz, int nc, f
     const int y = blockIdx.y, z = blockIdx.z;
     if (x >= dnx) return;
     const double xd = (double)x, yd = (double)y, zd = (double)z;
-    const double tx = A.a[0] * xd + A.a[1] * yd + A.a[2] * zd + A.a[3];
-    const double ty = A.a[4] * xd + A.a[5] * yd + A.a[6] * zd + A.a[7];
-    const double tz = A.a[8] * xd + A.a[9] * yd + A.a[10] * zd + A.a[11];
+    double tx, ty, tz;
+    s3d_affine_xyz(A, xd, yd, zd, tx, ty, tz);
     float *out = dst + (((size_t)z * dny + y) * dnx + x) * nc;
     s3d_sample_store<INTERP>(src, snx, sny, snz, nc, out, tx, ty, tz);
 }
@@ -119,20 +133,19 @@ extern "C" int s3d_k_inv_affine(const float *d_src, int snx, int sny, int snz, i
  * points in 22.6 ms, 82 % of the f64 issue rate, profiles/tps_warp_cost.txt); r2 == 0 is tested explicitly, since control points sit on voxels of the output grid and 0 * log(0) is NaN.  The
  * tail -- the constant, then the x, y and z terms -- is the reference's expression, separately rounded (this file is compiled
  * without contraction), so n_ctrl = 0 gives the reference's bits.  No lane leaves before the last barrier. */
-template <int INTERP>
-__global__ void __launch_bounds__(256)
-k_inv_tps(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny, int dnz,
-          const double *__restrict__ ctrl, const double *__restrict__ params, uint32_t n_ctrl)
+/* The spline's coordinates of voxel (xd, yd, zd) for every thread of a 256-thread workgroup: the control-point loop through
+ * the LDS tile s_pt (S3D_TPS_TILE * 6 doubles), then the tail.  Collective: every thread of the workgroup calls it, the same
+ * number of times (it holds barriers).  again: s_pt may still be read from an earlier call of this workgroup.  Shared by the
+ * spline warp and the spline similarity kernel. */
+__device__ __forceinline__ void s3d_tps_xyz(double *s_pt, const double *__restrict__ ctrl, const double *__restrict__ params,
+                                            uint32_t n_ctrl, bool again, double xd, double yd, double zd, double &tx_out,
+                                            double &ty_out, double &tz_out)
 {
-    __shared__ double s_pt[S3D_TPS_TILE * 6];               /* per point: x y z w_x w_y w_z */
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y = blockIdx.y, z = blockIdx.z;
-    const double xd = (double)x, yd = (double)y, zd = (double)z;
     const size_t row = (size_t)n_ctrl + 4;                  /* row length of params */
     double tx = 0.0, ty = 0.0, tz = 0.0;
     for (uint32_t n0 = 0; n0 < n_ctrl; n0 += S3D_TPS_TILE) {
         const uint32_t nt = n_ctrl - n0 < (uint32_t)S3D_TPS_TILE ? n_ctrl - n0 : (uint32_t)S3D_TPS_TILE;
-        if (n0) __syncthreads();                            /* the previous tile has been read by every lane */
+        if (n0 || again) __syncthreads();                   /* the previous tile has been read by every lane */
         for (uint32_t e = threadIdx.x; e < nt * 6u; e += 256u) {
             const uint32_t j = e / 6u, k = e - j * 6u;
             s_pt[e] = k < 3u ? ctrl[(size_t)(n0 + j) * 3 + k] : params[(size_t)(k - 3u) * row + n0 + j];
@@ -148,11 +161,25 @@ k_inv_tps(const float *__restrict__ src, int snx, int sny, int snz, int nc, floa
             tz = fma(u, p[5], tz);
         }
     }
-    if (x >= dnx) return;
     const double *ax = params + n_ctrl, *ay = ax + row, *az = ay + row;
     tx += ax[0]; tx += ax[1] * xd; tx += ax[2] * yd; tx += ax[3] * zd;
     ty += ay[0]; ty += ay[1] * xd; ty += ay[2] * yd; ty += ay[3] * zd;
     tz += az[0]; tz += az[1] * xd; tz += az[2] * yd; tz += az[3] * zd;
+    tx_out = tx; ty_out = ty; tz_out = tz;
+}
+
+template <int INTERP>
+__global__ void __launch_bounds__(256)
+k_inv_tps(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny, int dnz,
+          const double *__restrict__ ctrl, const double *__restrict__ params, uint32_t n_ctrl)
+{
+    __shared__ double s_pt[S3D_TPS_TILE * 6];               /* per point: x y z w_x w_y w_z */
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, z = blockIdx.z;
+    const double xd = (double)x, yd = (double)y, zd = (double)z;
+    double tx, ty, tz;
+    s3d_tps_xyz(s_pt, ctrl, params, n_ctrl, false, xd, yd, zd, tx, ty, tz);
+    if (x >= dnx) return;
     float *out = dst + (((size_t)z * dny + y) * dnx + x) * nc;
     s3d_sample_store<INTERP>(src, snx, sny, snz, nc, out, tx, ty, tz);
 }
@@ -227,6 +254,293 @@ extern "C" int s3d_k_ransac_count(const double *d_src, const double *d_ref, uint
     S3D_HIP(hipMemsetAsync(d_counts, 0, (size_t)nmodels * sizeof(int), (hipStream_t)stream));
     hipLaunchKernelGGL(k_ransac_count, dim3(s3d_div_up(npts, 256), gy), dim3(256), 0, (hipStream_t)stream, d_src, d_ref, npts,
                        d_models, nmodels, thr2, d_counts);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* ---- similarity of a source under a transform against a reference (sift3d_amd_im_similarity) -------------------------------
+ * The warp's pass -- every reference voxel through the transform, the source sampled there -- that accumulates instead of
+ * storing: the joint histogram of (reference voxel a, sample b) and seven f64 sums over the overlap, the voxels that
+ * s3d_sample_store samples and whose two values are finite.  The warped volume is never written.  The coordinates come from
+ * s3d_affine_xyz / s3d_tps_xyz and the sample from s3d_sample_store, the functions of the warp kernels, so a voxel's (a, b) is
+ * what im_inv_transform would have stored beside the reference.
+ *
+ * Workgroups are persistent: workgroup g walks the reference rows g, g + G, g + 2G, .. (a row: rnx voxels at one y, z), 256
+ * x-consecutive voxels at a time, G = s3d_sim_grid(rows, rnx, bins) -- a function of the dimensions and the bin count alone, so the
+ * voxels of a thread, and with them every f64 sum, are the same in every call.  The joint histogram is private to the workgroup
+ * in LDS, bins^2 32-bit counters (4 bins^2 bytes: 16 KiB at 64 bins, 64 KiB at 128; the launcher keeps the voxels of a
+ * workgroup below 2^32), and is flushed once, non-zero counters only, with 64-bit integer atomicAdds: integer sums do not depend
+ * on the order.  The seven sums have no atomics: a thread's registers, then the wave by shuffles, the four waves through LDS in
+ * wave order, and the workgroup's seven partials to its own slot of the scratch; k_sim_finish adds the slots in a fixed order
+ * (lane l takes slots l, l + 64, .., then the same shuffle tree).  The spline form stages the control points through LDS as
+ * k_inv_tps does; there every thread of the workgroup stays in the loop (s3d_tps_xyz holds barriers).
+ * AGG: one round of wave-level aggregation before the LDS atomic (s3d_k_similarity_set_aggregate).  Measured, it does not pay:
+ * same-counter atomics of a wave cost nothing visible even with 98 % of the voxels in one bin (profiles/similarity_cost.txt). */
+struct SimBins { double ref_lo, ref_scale, src_lo, src_scale, c_ref, c_src; };
+#define S3D_SIM_NSUM 7
+#define S3D_SIM_AGGREGATE_DEFAULT 0                         /* decided by profiles/similarity_cost.txt */
+#define S3D_SIM_CUS 256                                     /* the MI355X's compute units: the grid is a constant of the build */
+
+__device__ __forceinline__ bool s3d_finite_f(float v) { return fabsf(v) <= 3.4028234663852886e38f; }   /* false for NaN */
+
+__device__ __forceinline__ int s3d_sim_bin(float v, double lo, double scale, int bins)
+{
+    const double t = ((double)v - lo) * scale;
+    return t < 0 ? 0 : t >= bins ? bins - 1 : (int)t;
+}
+
+/* sum over the wave to lane 0, a fixed tree */
+__device__ __forceinline__ double s3d_wave_sum_f64(double v)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+    return v;
+}
+
+/* workgroups of a similarity launch: as many as the LDS (160 KiB per CU; the histogram, the spline tile, the partials) and
+ * the wave slots (8 workgroups of 4 waves) let be resident on S3D_SIM_CUS compute units, no more than there are rows, and no
+ * more than give every workgroup S3D_SIM_MIN_VOX voxels (its histogram is cleared and flushed, its sums reduced, once) */
+#define S3D_SIM_MIN_VOX 2048
+static unsigned s3d_sim_grid(size_t rows, size_t rnx, int bins)
+{
+    const size_t lds = (size_t)4 * bins * bins + S3D_TPS_TILE * 6 * sizeof(double) + 4 * S3D_SIM_NSUM * sizeof(double);
+    size_t per_cu = (size_t)160 * 1024 / lds;
+    if (per_cu > 8) per_cu = 8;
+    size_t g = (size_t)S3D_SIM_CUS * per_cu;
+    const size_t by_work = (rows * rnx + S3D_SIM_MIN_VOX - 1) / S3D_SIM_MIN_VOX;
+    if (g > by_work) g = by_work;
+    return (unsigned)(rows < g ? rows : g);
+}
+
+template <int INTERP, bool TPS, bool AGG>
+__global__ void __launch_bounds__(256)
+k_similarity(const float *__restrict__ src, int snx, int sny, int snz, const float *__restrict__ ref, int rnx, int rny,
+             uint32_t rows, AffineD A, const double *__restrict__ ctrl, const double *__restrict__ params, uint32_t n_ctrl,
+             int bins, SimBins R, unsigned long long *__restrict__ hist, double *__restrict__ partials)
+{
+    S3D_DYN_LDS(uint32_t, s_hist);                          /* bins * bins counters, row = reference bin */
+    __shared__ double s_pt[TPS ? S3D_TPS_TILE * 6 : 1];
+    __shared__ double s_red[4][S3D_SIM_NSUM];
+    const uint32_t tid = threadIdx.x, nb2 = (uint32_t)(bins * bins);
+    for (uint32_t i = tid; i < nb2; i += 256u) s_hist[i] = 0u;
+    __syncthreads();
+    double sum[S3D_SIM_NSUM];
+    for (int k = 0; k < S3D_SIM_NSUM; k++) sum[k] = 0.0;
+    bool again = false;
+    for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const uint32_t z = row / (uint32_t)rny, y = row - z * (uint32_t)rny;
+        const double yd = (double)y, zd = (double)z;
+        for (int x0 = 0; x0 < rnx; x0 += 256) {
+            const int x = x0 + (int)tid;
+            const double xd = (double)x;
+            double tx, ty, tz;
+            if (TPS) {
+                s3d_tps_xyz(s_pt, ctrl, params, n_ctrl, again, xd, yd, zd, tx, ty, tz);
+                again = true;
+            } else {
+                s3d_affine_xyz(A, xd, yd, zd, tx, ty, tz);
+            }
+            int cell = -1;                                  /* the voxel's counter; -1: not in the overlap */
+            if (x < rnx && s3d_sample_inside(snx, sny, snz, tx, ty, tz)) {
+                const float a = ref[(size_t)row * rnx + x];
+                float b;
+                s3d_sample_store<INTERP>(src, snx, sny, snz, 1, &b, tx, ty, tz);
+                if (s3d_finite_f(a) && s3d_finite_f(b)) {
+                    const int ia = s3d_sim_bin(a, R.ref_lo, R.ref_scale, bins), ib = s3d_sim_bin(b, R.src_lo, R.src_scale, bins);
+                    cell = ia * bins + ib;
+                    const double ap = (double)a - R.c_ref, bp = (double)b - R.c_src, d = (double)a - (double)b;
+                    sum[0] += ap;
+                    sum[1] += bp;
+                    sum[2] += ap * ap;
+                    sum[3] += bp * bp;
+                    sum[4] += ap * bp;
+                    sum[5] += d * d;
+                    sum[6] += fabs(d);
+                }
+            }
+            if (AGG) {
+                /* one round of wave-level aggregation: the lanes that share the first counted lane's counter add their number
+                 * with one atomic (the background bin of a medical volume), the others add one each */
+                const unsigned long long counted = __ballot(cell >= 0);
+                if (counted) {                              /* wave-uniform */
+                    const int first = __ffsll(counted) - 1;
+                    const int c0 = __shfl(cell, first);
+                    const unsigned long long same = __ballot(cell == c0);
+                    if (cell == c0) {
+                        if ((int)(tid & 63u) == first) atomicAdd(&s_hist[c0], (uint32_t)__popcll(same));
+                    } else if (cell >= 0) {
+                        atomicAdd(&s_hist[cell], 1u);
+                    }
+                }
+            } else if (cell >= 0) {
+                atomicAdd(&s_hist[cell], 1u);
+            }
+        }
+    }
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    for (int k = 0; k < S3D_SIM_NSUM; k++) {
+        const double v = s3d_wave_sum_f64(sum[k]);
+        if (lane == 0) s_red[wave][k] = v;
+    }
+    __syncthreads();                                        /* the histogram is complete, the waves' sums are in LDS */
+    if (tid < S3D_SIM_NSUM)
+        partials[(size_t)blockIdx.x * S3D_SIM_NSUM + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    for (uint32_t i = tid; i < nb2; i += 256u) {
+        const uint32_t c = s_hist[i];
+        if (c) atomicAdd(&hist[i], (unsigned long long)c);
+    }
+}
+
+/* sums[k] = the slots' k-th partials, added in a fixed order: wave k of 7, lane l takes slots l, l + 64, .. */
+__global__ void __launch_bounds__(64 * S3D_SIM_NSUM)
+k_sim_finish(const double *__restrict__ partials, uint32_t nslots, double *__restrict__ sums)
+{
+    const uint32_t lane = threadIdx.x & 63u, k = threadIdx.x >> 6;
+    double v = 0.0;
+    for (uint32_t s = lane; s < nslots; s += 64u) v += partials[(size_t)s * S3D_SIM_NSUM + k];
+    v = s3d_wave_sum_f64(v);
+    if (lane == 0) sums[k] = v;
+}
+
+/* whether the calling thread's launches aggregate equal counters within a wave before the LDS atomic (profiling knob) */
+static thread_local int g_sim_aggregate = S3D_SIM_AGGREGATE_DEFAULT;
+extern "C" void s3d_k_similarity_set_aggregate(int on) { g_sim_aggregate = on < 0 ? S3D_SIM_AGGREGATE_DEFAULT : on != 0; }
+extern "C" int s3d_k_similarity_get_aggregate(void) { return g_sim_aggregate; }
+
+extern "C" size_t s3d_k_similarity_scratch_bytes(int rnx, int rny, int rnz, int bins)
+{
+    if (rnx < 1 || rny < 1 || rnz < 1 || bins < 2 || bins > S3D_SIM_MAX_BINS) return 0;
+    return (size_t)s3d_sim_grid((size_t)rny * rnz, (size_t)rnx, bins) * S3D_SIM_NSUM * sizeof(double);
+}
+
+/* a histogram of 128 bins is 64 KiB of dynamic LDS beside the static tiles, above what a launch gets by default: raise the
+ * limit of the four kernels once per device, as s3d_k_describe does for its kernel */
+static int s3d_sim_prepare(void)
+{
+#if !defined(S3D_EMU)
+    static unsigned char done[64];
+    int dev = 0;
+    S3D_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        const int bytes = 4 * S3D_SIM_MAX_BINS * S3D_SIM_MAX_BINS;
+#define S3D_SIM_RAISE(I, T, G) \
+    S3D_HIP(hipFuncSetAttribute((const void *)k_similarity<I, T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes))
+        S3D_SIM_RAISE(0, false, false); S3D_SIM_RAISE(1, false, false); S3D_SIM_RAISE(0, true, false); S3D_SIM_RAISE(1, true, false);
+        S3D_SIM_RAISE(0, false, true); S3D_SIM_RAISE(1, false, true); S3D_SIM_RAISE(0, true, true); S3D_SIM_RAISE(1, true, true);
+#undef S3D_SIM_RAISE
+        if (dev >= 0 && dev < 64) done[dev] = 1;
+    }
+#endif
+    return S3D_OK;
+}
+
+static int s3d_sim_launch(bool tps, const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                          const double A[12], const double *d_ctrl, const double *d_params, uint32_t n_ctrl, int interp, int bins,
+                          double ref_lo, double ref_scale, double src_lo, double src_scale, double c_ref, double c_src,
+                          unsigned long long *d_hist, double *d_sums, void *d_scratch, s3d_stream stream)
+{
+    if (snx < 1 || sny < 1 || snz < 1 || rnx < 1 || rny < 1 || rnz < 1) S3D_FAIL("bad dimensions");
+    if (bins < 2 || bins > S3D_SIM_MAX_BINS) S3D_FAIL("bins outside 2 .. 128");
+    if (interp != 0 && interp != 1) S3D_FAIL("unrecognized interpolation type");
+    if (d_src == NULL || d_ref == NULL || d_hist == NULL || d_sums == NULL || d_scratch == NULL) S3D_FAIL("missing buffer");
+    if (tps && (d_params == NULL || (n_ctrl > 0 && d_ctrl == NULL))) S3D_FAIL("missing spline parameters");
+    const size_t rows = (size_t)rny * rnz;
+    if (rows > 0x7fffffffu) S3D_FAIL("volume too large for the similarity grid");
+    const unsigned grid = s3d_sim_grid(rows, (size_t)rnx, bins);
+    /* a workgroup's 32-bit counters: its rows times the row length */
+    if ((rows + grid - 1) / grid * (size_t)rnx > 0xffffffffu) S3D_FAIL("volume too large for the workgroups' 32-bit counters");
+    if (s3d_sim_prepare()) return S3D_ERR;
+    AffineD a;
+    for (int i = 0; i < 12; i++) a.a[i] = A ? A[i] : 0.0;
+    const SimBins R = {ref_lo, ref_scale, src_lo, src_scale, c_ref, c_src};
+    const size_t lds = (size_t)4 * bins * bins;
+    double *part = (double *)d_scratch;
+    S3D_HIP(hipMemsetAsync(d_hist, 0, (size_t)bins * bins * sizeof(unsigned long long), (hipStream_t)stream));
+#define S3D_SIM_GO(I, T, G)                                                                                                       \
+    hipLaunchKernelGGL((k_similarity<I, T, G>), dim3(grid), dim3(256), lds, (hipStream_t)stream, d_src, snx, sny, snz, d_ref, rnx, \
+                       rny, (uint32_t)rows, a, d_ctrl, d_params, n_ctrl, bins, R, d_hist, part)
+#define S3D_SIM_GO2(I, T) do { if (g_sim_aggregate) S3D_SIM_GO(I, T, true); else S3D_SIM_GO(I, T, false); } while (0)
+    if (tps) { if (interp == 0) S3D_SIM_GO2(0, true); else S3D_SIM_GO2(1, true); }
+    else { if (interp == 0) S3D_SIM_GO2(0, false); else S3D_SIM_GO2(1, false); }
+#undef S3D_SIM_GO2
+#undef S3D_SIM_GO
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sim_finish, dim3(1), dim3(64 * S3D_SIM_NSUM), 0, (hipStream_t)stream, part, (uint32_t)grid, d_sums);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+extern "C" int s3d_k_similarity_affine(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny,
+                                       int rnz, const double A[12], int interp, int bins, double ref_lo, double ref_scale,
+                                       double src_lo, double src_scale, double c_ref, double c_src, unsigned long long *d_hist,
+                                       double *d_sums, void *d_scratch, s3d_stream stream)
+{
+    if (A == NULL) S3D_FAIL("missing affine matrix");
+    return s3d_sim_launch(false, d_src, snx, sny, snz, d_ref, rnx, rny, rnz, A, NULL, NULL, 0, interp, bins, ref_lo, ref_scale,
+                          src_lo, src_scale, c_ref, c_src, d_hist, d_sums, d_scratch, stream);
+}
+
+extern "C" int s3d_k_similarity_tps(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                    const double *d_ctrl, const double *d_params, uint32_t n_ctrl, int interp, int bins,
+                                    double ref_lo, double ref_scale, double src_lo, double src_scale, double c_ref, double c_src,
+                                    unsigned long long *d_hist, double *d_sums, void *d_scratch, s3d_stream stream)
+{
+    return s3d_sim_launch(true, d_src, snx, sny, snz, d_ref, rnx, rny, rnz, NULL, d_ctrl, d_params, n_ctrl, interp, bins, ref_lo,
+                          ref_scale, src_lo, src_scale, c_ref, c_src, d_hist, d_sums, d_scratch, stream);
+}
+
+/* ---- minimum and maximum over the finite voxels (the default ranges of the joint histogram) --------------------------------
+ * Order-free: the bit pattern of a finite float under the usual order-preserving map to unsigned (negative: all bits flipped,
+ * else the sign bit set) is reduced with integer maxima only -- the maximum over the map, the minimum as the maximum over its
+ * complement -- so the result does not depend on the schedule.  Both encodings of a finite float are non-zero; a zero word
+ * after the pass says that no voxel was finite and decodes to NaN.  d_minmax: two floats, used as two words in between. */
+__device__ __forceinline__ uint32_t s3d_ord_f32(float v)
+{
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ void __launch_bounds__(256)
+k_minmax_finite(const float *__restrict__ v, size_t n, uint32_t *__restrict__ enc /* [0]: ~min, [1]: max */)
+{
+    uint32_t emax = 0u, emin = 0u;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
+        const float f = v[i];
+        if (s3d_finite_f(f)) {
+            const uint32_t e = s3d_ord_f32(f);
+            emax = e > emax ? e : emax;
+            emin = ~e > emin ? ~e : emin;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t omax = __shfl_down(emax, d), omin = __shfl_down(emin, d);
+        emax = omax > emax ? omax : emax;
+        emin = omin > emin ? omin : emin;
+    }
+    if ((threadIdx.x & 63u) == 0) {
+        if (emin) atomicMax(&enc[0], emin);
+        if (emax) atomicMax(&enc[1], emax);
+    }
+}
+
+__global__ void k_minmax_decode(uint32_t *enc)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t e[2] = {enc[0] ? ~enc[0] : 0u, enc[1]};
+    for (int k = 0; k < 2; k++) {
+        const uint32_t u = e[k] == 0u ? 0x7fc00000u : (e[k] & 0x80000000u) ? (e[k] & 0x7fffffffu) : ~e[k];
+        enc[k] = u;
+    }
+}
+
+extern "C" int s3d_k_minmax_finite(const float *d_v, size_t n, float *d_minmax, s3d_stream stream)
+{
+    if (n < 1 || d_v == NULL || d_minmax == NULL) S3D_FAIL("bad dimensions");
+    size_t g = (n + 256 * 16 - 1) / (256 * 16);
+    if (g > 2048) g = 2048;
+    S3D_HIP(hipMemsetAsync(d_minmax, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_minmax_finite, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, d_v, n, (uint32_t *)d_minmax);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_minmax_decode, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t *)d_minmax);
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }

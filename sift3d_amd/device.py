@@ -57,6 +57,10 @@ def bind_extensions(L: C.CDLL) -> None:
         L.resize_Tps.argtypes = [P(abi.Tps), C.c_int, C.c_int]
         L.sift3d_amd_fit_tps.argtypes = [P(abi.Mat_rm), P(abi.Mat_rm), C.c_double, P(abi.Tps)]
         L.sift3d_amd_register_tps.argtypes = [P(abi.Reg_SIFT3D), P(abi.TpsOpts), P(abi.Affine), P(abi.Tps)]
+    if hasattr(L, "sift3d_amd_im_similarity"):            # (absent from builds older than the similarity scores)
+        L.sift3d_amd_im_similarity.argtypes = [_vp, P(abi.Image), P(abi.Image), P(abi.SimilarityOpts), P(abi.Similarity), _vp]
+        L.sift3d_amd_similarity_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                P(abi.SimilarityOpts), P(abi.Similarity), _vp, _vp]
 
 
 class DeviceLib:
@@ -115,6 +119,17 @@ class DeviceLib:
         if hasattr(L, "s3d_k_inv_tps"):                   # (absent from builds older than the thin-plate spline)
             L.s3d_k_inv_tps.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp,
                                         C.c_uint32, C.c_int, _vp]
+        if hasattr(L, "s3d_k_similarity_affine"):         # (absent from builds older than the similarity scores)
+            _sim_tail = [C.c_int, C.c_int] + [C.c_double] * 6 + [_vp, _vp, _vp, _vp]   # interp, bins, range / scale / pivots, ...
+            L.s3d_k_similarity_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+            L.s3d_k_similarity_scratch_bytes.restype = C.c_size_t
+            L.s3d_k_similarity_affine.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_double)] + _sim_tail
+            L.s3d_k_similarity_tps.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                               C.c_uint32] + _sim_tail
+            L.s3d_k_minmax_finite.argtypes = [_vp, C.c_size_t, _vp, _vp]
+            L.s3d_k_similarity_set_aggregate.argtypes = [C.c_int]
+            L.s3d_k_similarity_set_aggregate.restype = None
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -245,6 +260,50 @@ class DeviceLib:
         1 Lanczos-2."""
         self.check(self.L.s3d_k_inv_tps(_vp(d_src), sdims[0], sdims[1], sdims[2], nc, _vp(d_dst), ddims[0], ddims[1], ddims[2],
                                         _vp(d_ctrl), _vp(d_params), n_ctrl, interp, _vp(stream)), "s3d_k_inv_tps")
+
+    # --- similarity of a source under a transform against a reference ---------------------------------------
+    def minmax_finite(self, d_v: int, n: int, stream=None) -> tuple:
+        """(min, max) over the finite elements of the n float32 at d_v; both NaN when none is (s3d_k_minmax_finite)."""
+        d_mm = self.malloc(8)
+        try:
+            self.check(self.L.s3d_k_minmax_finite(_vp(d_v), n, _vp(d_mm), _vp(stream)), "s3d_k_minmax_finite")
+            mm = self.download(d_mm, (2,), np.float32, stream)
+        finally:
+            self.free(d_mm)
+        return float(mm[0]), float(mm[1])
+
+    def _similarity(self, launch, rdims, bins: int, stream):
+        nbytes = int(self.L.s3d_k_similarity_scratch_bytes(rdims[0], rdims[1], rdims[2], bins))
+        if nbytes == 0:
+            raise RuntimeError("s3d_k_similarity_scratch_bytes: bad dimensions or bins")
+        d_hist, d_sums, d_scr = self.malloc(bins * bins * 8), self.malloc(7 * 8), self.malloc(nbytes)
+        try:
+            launch(d_hist, d_sums, d_scr)
+            return (self.download(d_hist, (bins, bins), np.uint64, stream), self.download(d_sums, (7,), np.float64, stream))
+        finally:
+            for p in (d_hist, d_sums, d_scr):
+                self.free(p)
+
+    def similarity_affine(self, d_src: int, sdims, d_ref: int, rdims, A, interp: int, bins: int, ref_lo: float,
+                          ref_scale: float, src_lo: float, src_scale: float, c_ref: float, c_src: float, stream=None) -> tuple:
+        """(joint histogram uint64 [bins, bins], row = reference bin; the seven float64 sums) of d_src (sdims = (nx, ny, nz),
+        float32, one channel) sampled at A [x y z 1]^T of every voxel of d_ref (rdims) -- s3d_k_similarity_affine; A: 12
+        doubles, 3 x 4 row major."""
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        return self._similarity(lambda h, s, w: self.check(self.L.s3d_k_similarity_affine(
+            _vp(d_src), sdims[0], sdims[1], sdims[2], _vp(d_ref), rdims[0], rdims[1], rdims[2],
+            a.ctypes.data_as(C.POINTER(C.c_double)), interp, bins, ref_lo, ref_scale, src_lo, src_scale, c_ref, c_src, _vp(h),
+            _vp(s), _vp(w), _vp(stream)), "s3d_k_similarity_affine"), rdims, bins, stream)
+
+    def similarity_tps(self, d_src: int, sdims, d_ref: int, rdims, d_ctrl: int | None, d_params: int, n_ctrl: int, interp: int,
+                       bins: int, ref_lo: float, ref_scale: float, src_lo: float, src_scale: float, c_ref: float, c_src: float,
+                       stream=None) -> tuple:
+        """The same through a spline (s3d_k_similarity_tps): d_ctrl n_ctrl x 3 and d_params 3 x (n_ctrl + 4) doubles on the
+        device, as for inv_tps."""
+        return self._similarity(lambda h, s, w: self.check(self.L.s3d_k_similarity_tps(
+            _vp(d_src), sdims[0], sdims[1], sdims[2], _vp(d_ref), rdims[0], rdims[1], rdims[2], _vp(d_ctrl), _vp(d_params),
+            n_ctrl, interp, bins, ref_lo, ref_scale, src_lo, src_scale, c_ref, c_src, _vp(h), _vp(s), _vp(w), _vp(stream)),
+            "s3d_k_similarity_tps"), rdims, bins, stream)
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
