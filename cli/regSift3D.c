@@ -6,7 +6,9 @@
  *               [--err_thresh v] [--num_iter n] [--type affine] [--resample] source.nii reference.nii
  * and, beyond the reference, [--tps] [--tps_lambda v] [--tps_thresh v] [--tps_max_points n]: a thin-plate spline fitted to
  * the matches near the affine map (sift3d_amd_register_tps), written by --transform and used by --warped, and
- * [--metrics m.csv] [--metric_bins n]: the similarity of the images before and after (sift3d_amd_im_similarity),
+ * [--metrics m.csv] [--metric_bins n]: the similarity of the images before and after (sift3d_amd_im_similarity), and
+ * [--refine] [--refine_levels n] [--refine_iter n] [--refine_normalize]: the affine map improved on the voxel intensities
+ * (sift3d_amd_refine_affine) before it is written, used by --warped and scored by --metrics,
  * linked against libsift3d_amd.so.  Detection, description, matching and the warp run as HIP kernels;
  * RANSAC is host C.  As in the reference, --err_thresh and --num_iter are parsed after the Ransac
  * parameters have been copied into the registration object, so they do not reach the estimator
@@ -64,11 +66,25 @@ static void usage(void)
            "Similarity options: \n"
            " --metrics [filename] - How well the images agree, one row per \n"
            "       stage: before registration, under the affine fit and, \n"
-           "       with --tps, under the spline. Columns: n (voxels of the \n"
-           "       overlap), n_total, mse, mae, ncc, mi, nmi. \n"
+           "       with --tps or --refine, under the spline or the refined \n"
+           "       map. Columns: n (voxels of the overlap), n_total, mse, \n"
+           "       mae, ncc, mi, nmi. \n"
            "       Supported file formats: .csv, .csv.gz \n"
            " --metric_bins [value] - Bins per axis of the joint histogram \n"
            "       behind mi and nmi, in the interval [2, %d]. (default: %d) \n"
+           "\n"
+           "Refinement options: \n"
+           " --refine - After the affine fit, improve it on the voxel \n"
+           "       intensities (Levenberg-Marquardt on the squared \n"
+           "       difference over the overlap, coarse to fine). \n"
+           "       --transform and --warped then use the refined map and \n"
+           "       --metrics gets a row for it. \n"
+           " --refine_levels [value] - Pyramid levels, at least 1. \n"
+           "       (default: %d) \n"
+           " --refine_iter [value] - Largest number of accepted steps per \n"
+           "       level, at least 1. (default: %d) \n"
+           " --refine_normalize - Compare z-scored intensities: for images \n"
+           "       that differ by a gain and an offset. \n"
            "\n"
            "Other options: \n"
            " --nn_thresh [value] - Matching threshold on the nearest neighbor \n"
@@ -85,7 +101,7 @@ static void usage(void)
            "	to 1mm slices. \n"
            "\n",
            SIFT3D_AMD_TPS_LAMBDA_DEFAULT, SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT, SIFT3D_AMD_SIMILARITY_BINS_MAX,
-           SIFT3D_AMD_SIMILARITY_BINS_DEFAULT, SIFT3D_nn_thresh_default,
+           SIFT3D_AMD_SIMILARITY_BINS_DEFAULT, SIFT3D_AMD_REFINE_LEVELS_DEFAULT, SIFT3D_AMD_REFINE_ITER_DEFAULT, SIFT3D_nn_thresh_default,
            SIFT3D_err_thresh_default, SIFT3D_num_iter_default);
     print_opts_SIFT3D();
 }
@@ -111,7 +127,7 @@ static void complain_path(const char *what, const char *path)
 int main(int argc, char *argv[])
 {
     enum { MATCHES = 'a', TRANSFORM, WARPED, CONCAT, KEYS, LINES, NN_THRESH, ERR_THRESH, NUM_ITER, TYPE, RESAMPLE, TPS_FIT, TPS_LAMBDA,
-           TPS_THRESH, TPS_MAX_POINTS, METRICS, METRIC_BINS };
+           TPS_THRESH, TPS_MAX_POINTS, METRICS, METRIC_BINS, REFINE, REFINE_LEVELS, REFINE_ITER, REFINE_NORMALIZE };
     static const struct option longopts[] = {{"matches", required_argument, NULL, MATCHES},
                                              {"transform", required_argument, NULL, TRANSFORM},
                                              {"warped", required_argument, NULL, WARPED},
@@ -129,6 +145,10 @@ int main(int argc, char *argv[])
                                              {"tps_max_points", required_argument, NULL, TPS_MAX_POINTS},
                                              {"metrics", required_argument, NULL, METRICS},
                                              {"metric_bins", required_argument, NULL, METRIC_BINS},
+                                             {"refine", no_argument, NULL, REFINE},
+                                             {"refine_levels", required_argument, NULL, REFINE_LEVELS},
+                                             {"refine_iter", required_argument, NULL, REFINE_ITER},
+                                             {"refine_normalize", no_argument, NULL, REFINE_NORMALIZE},
                                              {0, 0, 0, 0}};
     Reg_SIFT3D reg;
     SIFT3D sift3d;
@@ -141,7 +161,8 @@ int main(int argc, char *argv[])
     const char *match_path = NULL, *tform_path = NULL, *warped_path = NULL, *concat_path = NULL, *keys_path = NULL,
                *lines_path = NULL, *metrics_path = NULL;
     sift3d_amd_similarity_opts sim_opts = {0, LINEAR, {0.0, 0.0}, {0.0, 0.0}};   /* the library's defaults */
-    int have_match = 0, have_tform = 0, resample = 0, use_tps = 0;
+    sift3d_amd_refine_opts refine_opts = {0, 0, 0.0, 0.0, 0};                    /* the library's defaults */
+    int have_match = 0, have_tform = 0, resample = 0, use_tps = 0, refine = 0;
 
     switch (parse_gnu(argc, argv)) {
     case SIFT3D_HELP: usage(); return 0;
@@ -208,6 +229,16 @@ int main(int argc, char *argv[])
             sim_opts.bins = atoi(optarg);
             if (sim_opts.bins < 2 || sim_opts.bins > SIFT3D_AMD_SIMILARITY_BINS_MAX) { complain("Invalid value for metric_bins."); return 1; }
             break;
+        case REFINE: refine = 1; break;
+        case REFINE_LEVELS:
+            refine_opts.levels = atoi(optarg);
+            if (refine_opts.levels < 1) { complain("Invalid value for refine_levels."); return 1; }
+            break;
+        case REFINE_ITER:
+            refine_opts.max_iter = atoi(optarg);
+            if (refine_opts.max_iter < 1) { complain("Invalid value for refine_iter."); return 1; }
+            break;
+        case REFINE_NORMALIZE: refine_opts.normalize = 1; break;
         default: return 1;
         }
     }
@@ -217,6 +248,9 @@ int main(int argc, char *argv[])
     const char *src_path = argv[optind], *ref_path = argv[optind + 1];
     if (use_tps && resample) { complain("--tps cannot be combined with --resample."); return 1; }
     if (metrics_path != NULL && resample) { complain("--metrics cannot be combined with --resample."); return 1; }
+    if (refine && resample) { complain("--refine cannot be combined with --resample."); return 1; }
+    if (refine && use_tps) { complain("--refine cannot be combined with --tps."); return 1; }
+    refine = refine && have_tform;                     /* the refined map only shows in --transform, --warped and --metrics */
     use_tps = use_tps && have_tform;                   /* the spline only shows in --transform, --warped and --metrics */
     if (init_tform(&tform, AFFINE) || init_Tps(&tps, IM_NDIMS, IM_NDIMS + 1)) return 1;
     if (im_read(src_path, &src)) { complain_path("Failed to read the source image", src_path); return 1; }
@@ -249,14 +283,24 @@ int main(int argc, char *argv[])
         if (write_Mat_rm(match_path, &matches)) { complain_path("Failed to write the matches", match_path); return 1; }
         cleanup_Mat_rm(&matches);
     }
-    const void *const tform_out = use_tps ? (const void *)&tps : (const void *)&tform;
+    Affine refined;                                    /* tform stays the keypoint fit: --metrics scores both */
+    if (init_tform(&refined, AFFINE)) return 1;
+    if (refine) {
+        sift3d_amd_refine_info rinfo;
+        if (copy_tform(&tform, &refined) || sift3d_amd_refine_affine(&src, &ref, &refine_opts, &refined, &rinfo)) {
+            fprintf(stderr, "%s\n", sift3d_amd_last_error());
+            complain("Failed to refine the affine transformation.");
+            return 1;
+        }
+    }
+    const void *const tform_out = refine ? (const void *)&refined : use_tps ? (const void *)&tps : (const void *)&tform;
     if (tform_path != NULL && write_tform(tform_path, tform_out)) {
         complain_path("Failed to write the transformation parameters", tform_path);
         return 1;
     }
     if (metrics_path != NULL) {                        /* one row per stage, on the images as read */
-        const void *const stages[3] = {NULL, &tform, &tps};
-        const int nstages = use_tps ? 3 : 2;
+        const void *const stages[3] = {NULL, &tform, refine ? (const void *)&refined : (const void *)&tps};
+        const int nstages = use_tps || refine ? 3 : 2;
         Mat_rm metrics;
         if (init_Mat_rm(&metrics, nstages, 7, SIFT3D_DOUBLE, SIFT3D_TRUE)) { complain_bug("Failed to allocate the metrics."); return 1; }
         for (int i = 0; i < nstages; i++) {
@@ -308,6 +352,7 @@ int main(int argc, char *argv[])
     }
     cleanup_tform(&tform);
     cleanup_tform(&tps);
+    cleanup_tform(&refined);
     cleanup_Mat_rm(&match_src);
     cleanup_Mat_rm(&match_ref);
     cleanup_Reg_SIFT3D(&reg);

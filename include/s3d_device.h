@@ -477,6 +477,38 @@ int s3d_k_similarity_get_aggregate(void);
  * Integer maxima over an order-preserving encoding: the result does not depend on the schedule. */
 int s3d_k_minmax_finite(const float *d_v, size_t n, float *d_minmax, s3d_stream stream);
 
+/* ---- normal equations of an intensity-based affine fit (s3d_resample.hip; extension, sift3d_amd_refine_affine) --------------
+ * One pass over the reference volume d_ref (rnx x rny x rnz) against the source d_src (snx x sny x snz), both one channel with
+ * default strides: the sums of one Gauss-Newton step on the 12 entries of the affine map A (3 x 4 row major, reference voxel ->
+ * source voxel coordinates), for the residual r = sb (b - mb) - sa (a - ma).  Raw SSD is (sa, ma, sb, mb) = (1, 0, 1, 0).
+ * For every reference voxel (x, y, z), all in f64, every operation rounded on its own (no contraction), left to right:
+ *   (tx, ty, tz) = A [x y z 1]^T as s3d_k_inv_affine computes it;   q = (qx, qy, qz, 1) = (x - c[0], y - c[1], z - c[2], 1);
+ *   a = d_ref(x, y, z);   b = the float s3d_k_inv_affine (tri-linear) would store for this voxel;
+ *   X0 = min(floor(tx), snx - 2), fx = tx - X0, ux = 1 - fx, likewise Y0, fy, uy, Z0, fz, uz;  cijk = d_src(X0 + i, Y0 + j, Z0 + k);
+ *   gx = sb * (((c100 - c000) * uy + (c110 - c010) * fy) * uz + ((c101 - c001) * uy + (c111 - c011) * fy) * fz)
+ *   gy = sb * (((c010 - c000) * ux + (c110 - c100) * fx) * uz + ((c011 - c001) * ux + (c111 - c101) * fx) * fz)
+ *   gz = sb * (((c001 - c000) * ux + (c101 - c100) * fx) * uy + ((c011 - c010) * ux + (c111 - c110) * fx) * fy)
+ *       -- the gradient of the tri-linear interpolant on the cell [X0, X0 + 1] x .., one-sided on a lattice point and on the
+ *       last plane of an axis;
+ *   r = sb * ((double)b - mb) - sa * ((double)a - ma).
+ * The voxel counts iff s3d_k_inv_affine would sample it (no coordinate outside [0, n - 1], none NaN), a and b are finite floats
+ * and gx, gy, gz are finite.  d_sums, S3D_NEQ_SUMS = 74 doubles, over the counted voxels:
+ *   [P * 10 + Q], P < 6, Q < 10:  sum (g_i * g_j) * (q_k * q_l),  P the pair (i, j) of xx, xy, xz, yy, yz, zz and Q the pair
+ *       (k, l) of 00, 01, 02, 03, 11, 12, 13, 22, 23, 33 (q_3 = 1, so (q_k * q_3) is q_k and (q_3 * q_3) is 1).  The Jacobian row
+ *       of r in the entry (i, k) of [D | d] -- the step in centred coordinates, A <- A + D, t <- t + d - D c -- is g_i q_k, so
+ *       H[(i, k), (j, l)] = d_sums[P(i, j) * 10 + Q(k, l)];
+ *   [60 + i * 4 + k]:  sum (r * g_i) * q_k, the gradient's entry (i, k);      [72]: sum r * r;      [73]: n, the count.
+ * No floating-point atomics: per-workgroup partials in d_scratch, added by a second launch in a fixed order; which voxels a
+ * thread sums depends on the dimensions only, so a call's bits repeat on the same device and build.  n is exact.  d_scratch:
+ * s3d_k_affine_normal_eq_scratch_bytes(..) bytes (0: bad dimensions), owned by the call until it has run.  Fails with a message,
+ * the outputs untouched, for a dimension < 1, a source dimension < 2 (no gradient: H would be singular), more than 2^31 - 1 rows
+ * (rny * rnz) and NULL pointers. */
+#define S3D_NEQ_SUMS 74
+size_t s3d_k_affine_normal_eq_scratch_bytes(int rnx, int rny, int rnz);
+int s3d_k_affine_normal_eq(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                           const double A[12], const double c[3], double sa, double ma, double sb, double mb, double *d_sums,
+                           void *d_scratch, s3d_stream stream);
+
 /* ---- matcher (s3d_match.hip; replaces match_desc, sift.c:2892-2969) ------------------------------- */
 /* For each of the `na` query rows (row r = d_a + (d_a_sel ? d_a_sel[r] : r) * a_stride, 768 floats) the
  * smallest and second-smallest f64 sum of squared differences over the nb rows of d_b and the index of

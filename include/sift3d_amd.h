@@ -666,6 +666,62 @@ int sift3d_amd_similarity_dev(const void *tform, const float *d_src, int snx, in
                               const sift3d_amd_similarity_opts *opts, sift3d_amd_similarity *out,
                               unsigned long long *joint, void *hip_stream);
 
+/* ---- intensity-based refinement of an affine registration on the device ----------------------------------------------------
+ * Improves an affine map (reference voxel -> source voxel coordinates, what register_SIFT3D returns) on the voxel intensities:
+ * Levenberg-Marquardt on its 12 entries for the cost sum r^2 / n over the overlap, r = sb (b - mb) - sa (a - ma), a the
+ * reference voxel and b the tri-linear sample of the source (the pair sift3d_amd_im_similarity scores; the overlap is its
+ * overlap, less the voxels whose intensity gradient is not finite).  Every evaluation is one fused pass on the device
+ * (s3d_k_affine_normal_eq, include/s3d_device.h) that returns the cost and the normal equations together, so a rejected step
+ * costs one pass; the 12 x 12 system (H + lambda diag H) delta = -grad is solved on the host in f64, in coordinates centred on
+ * the reference volume.
+ *   Step rule: lambda starts at 1e-3; a step is accepted when the cost decreases and n >= min_overlap * (n at the level's
+ *       start; on level 0: n_before), then lambda / 10, else lambda * 10.  A level stops CONVERGED when an accepted step moves no
+ *       corner of ref by more than tol level-0 voxels (or the gradient is exactly zero), MAX_ITER after max_iter accepted steps,
+ *       STALLED when lambda exceeds 1e10.
+ *   Pyramid: coarse to fine on the device; level l is l rounds of (Gaussian of sigma 1 voxel, every second voxel), level voxel
+ *       i being level-0 voxel 2^l i in both volumes, so the linear part carries over and the translation scales by 2^-l.  A
+ *       level at which a dimension of either volume would fall below 16 is skipped.  Level 0 starts from the coarse levels'
+ *       result only if that is no worse there (cost and overlap) than the affine as given, else from the affine as given.
+ *   normalize = 1: sa = 1 / std(a), ma = mean(a), sb = 1 / std(b), mb = mean(b) over the overlap at the level's starting
+ *       transform (sift3d_amd_similarity_dev), frozen for the level; a variance that is not positive gives scale 1.  This makes
+ *       the cost blind to a gain and an offset between the volumes at the price of a small bias from the frozen constants.
+ *   Non-finite voxels are excluded per voxel as in the similarity overlap.  The Gaussian of the coarse levels spreads them over
+ *       its support; nothing is done about that.
+ * Returns SIFT3D_SUCCESS with *affine refined: its level-0 cost is <= the cost of the affine as given and its
+ * n >= min_overlap * n_before.  Where no such map was found, *affine is returned bit for bit as given with status UNCHANGED.
+ * info (may be NULL): status is the way level 0 ended unless UNCHANGED; iters counts the accepted steps behind the returned
+ * map, passes every normal-equation pass; costs are sum r^2 / n at level 0 with level 0's constants.
+ * SIFT3D_FAILURE with sift3d_amd_last_error set, *affine and *info untouched, for: no overlap at the start, nc != 1, NULL data, a
+ * source dimension < 2, a transform that is not a 3-D Affine, a NaN or negative option, and a device failure.  opts NULL: all
+ * defaults.  Device memory of a call is freed before it returns. */
+typedef struct {
+    int levels;          /* 0: 3.  pyramid levels, coarse to fine */
+    int max_iter;        /* 0: 30 accepted steps per level */
+    double tol;          /* 0: 1e-3 level-0 voxels */
+    double min_overlap;  /* 0: 0.5 */
+    int normalize;       /* 0: raw SSD.  1: z-scored */
+} sift3d_amd_refine_opts;
+#define SIFT3D_AMD_REFINE_CONVERGED 0
+#define SIFT3D_AMD_REFINE_MAX_ITER 1
+#define SIFT3D_AMD_REFINE_STALLED 2
+#define SIFT3D_AMD_REFINE_UNCHANGED 3
+typedef struct {
+    int status;                        /* SIFT3D_AMD_REFINE_* */
+    int levels_run, iters, passes;
+    long long n_before, n_after;       /* level 0 */
+    double cost_before, cost_after;    /* level 0 */
+    double max_corner_shift;           /* level-0 voxels: the largest displacement of a corner of ref, start against result */
+} sift3d_amd_refine_info;
+#define SIFT3D_AMD_REFINE_LEVELS_DEFAULT 3
+#define SIFT3D_AMD_REFINE_ITER_DEFAULT 30
+/* Host volumes: non-default strides are gathered, both volumes are uploaded, the map is refined, everything is freed. */
+int sift3d_amd_refine_affine(const Image *src, const Image *ref, const sift3d_amd_refine_opts *opts,
+                             Affine *affine /* in: the start; out: refined */, sift3d_amd_refine_info *info);
+/* Device-resident volumes (x fastest, default strides); the work is ordered on hip_stream and has completed on return. */
+int sift3d_amd_refine_affine_dev(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                 const sift3d_amd_refine_opts *opts, Affine *affine, sift3d_amd_refine_info *info,
+                                 void *hip_stream);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

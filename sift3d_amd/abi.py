@@ -149,6 +149,22 @@ class SimilarityOpts(C.Structure):
     _fields_ = [("bins", C.c_int), ("interp", C.c_int), ("ref_range", C.c_double * 2), ("src_range", C.c_double * 2)]
 
 
+class RefineOpts(C.Structure):
+    """``sift3d_amd_refine_opts``; a zero field takes its default (levels 3, max_iter 30, tol 1e-3, min_overlap 0.5)."""
+    _fields_ = [("levels", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double), ("min_overlap", C.c_double),
+                ("normalize", C.c_int)]
+
+
+class RefineInfo(C.Structure):
+    """``sift3d_amd_refine_info``: how sift3d_amd_refine_affine ended; costs and counts are level 0's."""
+    _fields_ = [("status", C.c_int), ("levels_run", C.c_int), ("iters", C.c_int), ("passes", C.c_int),
+                ("n_before", C.c_longlong), ("n_after", C.c_longlong), ("cost_before", C.c_double),
+                ("cost_after", C.c_double), ("max_corner_shift", C.c_double)]
+
+
+REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_STALLED, REFINE_UNCHANGED = 0, 1, 2, 3
+
+
 class Reg_SIFT3D(C.Structure):
     _fields_ = [("src_units", C.c_double * 3), ("ref_units", C.c_double * 3), ("sift3d", SIFT3D), ("ran", Ransac),
                 ("desc_src", SIFT3D_Descriptor_store), ("desc_ref", SIFT3D_Descriptor_store), ("match_src", Mat_rm),

@@ -1332,3 +1332,326 @@ done:
     s3d_rt_free(d_im[0]); s3d_rt_free(d_im[1]);
     return rc;
 }
+
+/* ---- intensity-based refinement of an affine map (sift3d_amd.h) --------------------------------------------------------------
+ * Levenberg-Marquardt on the 12 entries of the map.  The device returns the cost and the normal equations of a map in one pass
+ * (s3d_k_affine_normal_eq); the 12 x 12 solve, the step rule and the pyramid schedule are here.  The map is kept in level-0
+ * voxel coordinates throughout; a level sees it with the translation scaled by 2^-l. */
+#define S3D_REF_FAIL(...) do { s3d_api_set_error("sift3d_amd_refine_affine: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+#define S3D_REF_MAX_LEVELS 16
+#define S3D_REF_MIN_DIM 16
+#define S3D_REF_LAMBDA0 1e-3
+#define S3D_REF_LAMBDA_MAX 1e10
+
+typedef struct {
+    const float *src, *ref;                                 /* device */
+    int sd[3], rd[3];
+} s3d_ref_level;
+
+typedef struct {
+    s3d_ref_level lv[S3D_REF_MAX_LEVELS];
+    int nlv, passes;
+    double *d_sums;
+    void *d_scr, *stream;
+} s3d_ref_ctx;
+
+/* the sums of the level-0 map A0 on level l with the constants K = (sa, ma, sb, mb); -1: device failure */
+static int s3d_ref_pass(s3d_ref_ctx *const c, const int l, const double A0[12], const double K[4], double S[S3D_NEQ_SUMS])
+{
+    const s3d_ref_level *const v = &c->lv[l];
+    const double scale = ldexp(1.0, l), ctr[3] = {0.5 * (v->rd[0] - 1), 0.5 * (v->rd[1] - 1), 0.5 * (v->rd[2] - 1)};
+    double A[12];
+    memcpy(A, A0, sizeof(A));
+    for (int i = 0; i < 3; i++) A[i * 4 + 3] = A0[i * 4 + 3] / scale;
+    if (s3d_k_affine_normal_eq(v->src, v->sd[0], v->sd[1], v->sd[2], v->ref, v->rd[0], v->rd[1], v->rd[2], A, ctr, K[0], K[1], K[2],
+                               K[3], c->d_sums, c->d_scr, c->stream) ||
+        s3d_rt_d2h(S, c->d_sums, S3D_NEQ_SUMS * sizeof(double), c->stream) || s3d_rt_sync(c->stream))
+        return -1;
+    c->passes++;
+    return 0;
+}
+
+/* the largest displacement of a corner of the rd[0] x rd[1] x rd[2] volume between the maps A and B */
+static double s3d_ref_corner_shift(const double A[12], const double B[12], const int rd[3])
+{
+    double best = 0.0;
+    for (int k = 0; k < 8; k++) {
+        const double p[4] = {(k & 1) ? rd[0] - 1.0 : 0.0, (k & 2) ? rd[1] - 1.0 : 0.0, (k & 4) ? rd[2] - 1.0 : 0.0, 1.0};
+        double d2 = 0.0;
+        for (int i = 0; i < 3; i++) {
+            double d = 0.0;
+            for (int j = 0; j < 4; j++) d += (A[i * 4 + j] - B[i * 4 + j]) * p[j];
+            d2 += d * d;
+        }
+        if (!(d2 <= best * best)) best = sqrt(d2);          /* a NaN shift stays visible */
+    }
+    return best;
+}
+
+/* delta (12: entry (i, k) of [D | d] at [i * 4 + k]) from the sums S and the damping lambda; non-zero: no usable step */
+static int s3d_ref_solve(const double S[S3D_NEQ_SUMS], const double lambda, double delta[12])
+{
+    static const int P[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}}, Q[4][4] = {{0, 1, 2, 3}, {1, 4, 5, 6}, {2, 5, 7, 8}, {3, 6, 8, 9}};
+    double M[144];
+    int piv[12];
+    for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 4; k++)
+            for (int j = 0; j < 3; j++)
+                for (int m = 0; m < 4; m++) M[(i * 4 + k) * 12 + j * 4 + m] = S[P[i][j] * 10 + Q[k][m]];
+    for (int p = 0; p < 12; p++) {
+        M[p * 12 + p] += lambda * M[p * 12 + p];
+        delta[p] = -S[60 + p];
+    }
+    if (s3d_lu(M, 12, piv)) return 1;
+    s3d_lu_solve(M, piv, 12, delta, 1);
+    for (int p = 0; p < 12; p++)
+        if (!(fabs(delta[p]) <= DBL_MAX)) return 1;
+    return 0;
+}
+
+/* One level.  A (level 0 coordinates) and S, its sums on level l, are the start and become the result; n_floor: the smallest
+ * count a step may have.  *iters grows by the accepted steps.  Returns the status the level ended with, or -1. */
+static int s3d_ref_run_level(s3d_ref_ctx *const c, const int l, double A[12], const double K[4], double S[S3D_NEQ_SUMS],
+                             const double n_floor, const int max_iter, const double tol, int *const iters)
+{
+    const s3d_ref_level *const v = &c->lv[l];
+    const double scale = ldexp(1.0, l), ctr[3] = {0.5 * (v->rd[0] - 1), 0.5 * (v->rd[1] - 1), 0.5 * (v->rd[2] - 1)};
+    double lambda = S3D_REF_LAMBDA0;
+    int accepted = 0;
+    for (;;) {
+        int flat = 1;
+        for (int p = 0; p < 12; p++) flat = flat && S[60 + p] == 0.0;
+        if (flat) return SIFT3D_AMD_REFINE_CONVERGED;       /* a stationary point: every step would be zero */
+        double delta[12], B[12], T[S3D_NEQ_SUMS];
+        int ok = !s3d_ref_solve(S, lambda, delta);
+        if (ok) {
+            for (int i = 0; i < 3; i++) {
+                const double *const D = delta + i * 4;
+                for (int j = 0; j < 3; j++) B[i * 4 + j] = A[i * 4 + j] + D[j];
+                B[i * 4 + 3] = A[i * 4 + 3] + scale * (D[3] - (D[0] * ctr[0] + D[1] * ctr[1] + D[2] * ctr[2]));
+            }
+            if (s3d_ref_pass(c, l, B, K, T)) return -1;
+            ok = T[73] > 0.0 && T[73] >= n_floor && T[72] / T[73] < S[72] / S[73];
+        }
+        if (ok) {
+            const double shift = s3d_ref_corner_shift(A, B, c->lv[0].rd);
+            memcpy(A, B, sizeof(B));
+            memcpy(S, T, sizeof(T));
+            lambda /= 10.0;
+            accepted++;
+            (*iters)++;
+            if (shift <= tol) return SIFT3D_AMD_REFINE_CONVERGED;
+            if (accepted >= max_iter) return SIFT3D_AMD_REFINE_MAX_ITER;
+        } else {
+            lambda *= 10.0;
+            if (lambda > S3D_REF_LAMBDA_MAX) return SIFT3D_AMD_REFINE_STALLED;
+        }
+    }
+}
+
+/* K = (sa, ma, sb, mb) of a level at the level-0 map A0: (1, 0, 1, 0), or the z-score of both sides over the overlap */
+static int s3d_ref_constants(s3d_ref_ctx *const c, const int l, const Affine *const like, const double A0[12], const int normalize,
+                             double K[4])
+{
+    K[0] = K[2] = 1.0;
+    K[1] = K[3] = 0.0;
+    if (!normalize) return 0;
+    const s3d_ref_level *const v = &c->lv[l];
+    double A[12];
+    memcpy(A, A0, sizeof(A));
+    for (int i = 0; i < 3; i++) A[i * 4 + 3] = A0[i * 4 + 3] / ldexp(1.0, l);
+    Affine t = *like;
+    t.A.u.data_double = A;
+    sift3d_amd_similarity sim;
+    if (sift3d_amd_similarity_dev(&t, v->src, v->sd[0], v->sd[1], v->sd[2], v->ref, v->rd[0], v->rd[1], v->rd[2], NULL, &sim, NULL,
+                                  c->stream))
+        return -1;
+    if (sim.n > 0) {
+        K[0] = sim.var_ref > 0.0 && sim.var_ref <= DBL_MAX ? 1.0 / sqrt(sim.var_ref) : 1.0;
+        K[1] = fabs(sim.mean_ref) <= DBL_MAX ? sim.mean_ref : 0.0;
+        K[2] = sim.var_src > 0.0 && sim.var_src <= DBL_MAX ? 1.0 / sqrt(sim.var_src) : 1.0;
+        K[3] = fabs(sim.mean_src) <= DBL_MAX ? sim.mean_src : 0.0;
+    }
+    return 0;
+}
+
+static int s3d_refine_check(const sift3d_amd_refine_opts *const opts, const Affine *const affine)
+{
+    if (affine == NULL) S3D_REF_FAIL("NULL transform");
+    if (tform_get_type(affine) != AFFINE || affine->A.num_rows != IM_NDIMS || affine->A.num_cols != IM_NDIMS + 1 ||
+        affine->A.type != SIFT3D_DOUBLE || affine->A.u.data_double == NULL)
+        S3D_REF_FAIL("the transform must be a 3-D Affine");
+    if (opts != NULL) {
+        if (opts->levels < 0 || opts->max_iter < 0) S3D_REF_FAIL("levels and max_iter must not be negative (%d, %d)", opts->levels, opts->max_iter);
+        if (!(opts->tol >= 0.0) || !(opts->min_overlap >= 0.0)) S3D_REF_FAIL("tol and min_overlap must be numbers >= 0");
+        if (opts->normalize != 0 && opts->normalize != 1) S3D_REF_FAIL("normalize must be 0 or 1, not %d", opts->normalize);
+    }
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_refine_affine_dev(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                 const sift3d_amd_refine_opts *opts, Affine *affine, sift3d_amd_refine_info *info, void *hip_stream)
+{
+    if (s3d_refine_check(opts, affine)) return SIFT3D_FAILURE;
+    if (d_src == NULL || d_ref == NULL) S3D_REF_FAIL("NULL data");
+    if (snx < 1 || sny < 1 || snz < 1 || rnx < 1 || rny < 1 || rnz < 1) S3D_REF_FAIL("bad dimensions");
+    if (snx < 2 || sny < 2 || snz < 2) S3D_REF_FAIL("a source dimension below 2 has no intensity gradient (%d x %d x %d)", snx, sny, snz);
+    int levels = opts != NULL && opts->levels != 0 ? opts->levels : SIFT3D_AMD_REFINE_LEVELS_DEFAULT;
+    if (levels > S3D_REF_MAX_LEVELS) levels = S3D_REF_MAX_LEVELS;
+    const int max_iter = opts != NULL && opts->max_iter != 0 ? opts->max_iter : SIFT3D_AMD_REFINE_ITER_DEFAULT;
+    const double tol = opts != NULL && opts->tol != 0.0 ? opts->tol : 1e-3;
+    const double min_overlap = opts != NULL && opts->min_overlap != 0.0 ? opts->min_overlap : 0.5;
+    const int normalize = opts != NULL ? opts->normalize : 0;
+
+    /* the levels that exist, and one device block for them: the coarse volumes, the two work volumes of the Gaussian, the
+     * sums and the partials */
+    s3d_ref_ctx c;
+    memset(&c, 0, sizeof(c));
+    c.stream = hip_stream;
+    c.lv[0] = (s3d_ref_level){d_src, d_ref, {snx, sny, snz}, {rnx, rny, rnz}};
+    c.nlv = 1;
+    size_t off[S3D_REF_MAX_LEVELS][2], bytes = 0;
+#define S3D_REF_VOX(d) ((size_t)(d)[0] * (d)[1] * (d)[2])
+#define S3D_REF_ALIGN(b) (((b) + 255) & ~(size_t)255)
+    while (c.nlv < levels) {
+        const s3d_ref_level *const p = &c.lv[c.nlv - 1];
+        s3d_ref_level *const n = &c.lv[c.nlv];
+        int small = 0;
+        for (int k = 0; k < 3; k++) {
+            n->sd[k] = p->sd[k] / 2;
+            n->rd[k] = p->rd[k] / 2;
+            small = small || n->sd[k] < S3D_REF_MIN_DIM || n->rd[k] < S3D_REF_MIN_DIM;
+        }
+        if (small) break;                                   /* every coarser level would be smaller still */
+        off[c.nlv][0] = bytes; bytes += S3D_REF_ALIGN(S3D_REF_VOX(n->sd) * sizeof(float));
+        off[c.nlv][1] = bytes; bytes += S3D_REF_ALIGN(S3D_REF_VOX(n->rd) * sizeof(float));
+        c.nlv++;
+    }
+    const size_t nwork = S3D_REF_VOX(c.lv[0].sd) > S3D_REF_VOX(c.lv[0].rd) ? S3D_REF_VOX(c.lv[0].sd) : S3D_REF_VOX(c.lv[0].rd);
+    const size_t off_work = bytes;
+    if (c.nlv > 1) bytes += 2 * S3D_REF_ALIGN(nwork * sizeof(float));
+    const size_t off_sums = bytes;
+    bytes += S3D_REF_ALIGN(S3D_NEQ_SUMS * sizeof(double));
+    const size_t off_scr = bytes;
+    bytes += s3d_k_affine_normal_eq_scratch_bytes(rnx, rny, rnz);   /* the finest level has the most workgroups */
+    unsigned char *d_blk = NULL;
+    int rc = SIFT3D_FAILURE;
+    if (s3d_rt_malloc((void **)&d_blk, bytes)) goto dev_failed;
+    c.d_sums = (double *)(d_blk + off_sums);
+    c.d_scr = d_blk + off_scr;
+    if (c.nlv > 1) {
+        float taps[7], acc = 0;                             /* init_Gauss_filter at sigma = 1 */
+        for (int i = 0; i < 7; i++) {
+            const double x = ((double)i - 3) / (1.0 + DBL_EPSILON);
+            taps[i] = (float)exp(-0.5 * x * x);
+            acc += taps[i];
+        }
+        for (int i = 0; i < 7; i++) taps[i] /= acc;
+        static const float uf[3] = {1.0f, 1.0f, 1.0f};
+        float *const blur = (float *)(d_blk + off_work), *const tmp = (float *)(d_blk + off_work + S3D_REF_ALIGN(nwork * sizeof(float)));
+        for (int l = 1; l < c.nlv; l++) {
+            const s3d_ref_level *const p = &c.lv[l - 1];
+            float *const dst[2] = {(float *)(d_blk + off[l][0]), (float *)(d_blk + off[l][1])};
+            if (s3d_k_sep_fir(p->src, blur, tmp, p->sd[0], p->sd[1], p->sd[2], 1, uf, taps, 7, hip_stream) ||
+                s3d_k_decimate2(blur, p->sd[0], p->sd[1], p->sd[2], dst[0], hip_stream) ||
+                s3d_k_sep_fir(p->ref, blur, tmp, p->rd[0], p->rd[1], p->rd[2], 1, uf, taps, 7, hip_stream) ||
+                s3d_k_decimate2(blur, p->rd[0], p->rd[1], p->rd[2], dst[1], hip_stream))
+                goto dev_failed;
+            c.lv[l].src = dst[0];
+            c.lv[l].ref = dst[1];
+        }
+    }
+
+    double A_start[12], A[12], K[4], S_start[S3D_NEQ_SUMS], S[S3D_NEQ_SUMS];
+    static const double raw[4] = {1.0, 0.0, 1.0, 0.0};
+    memcpy(A_start, affine->A.u.data_double, sizeof(A_start));
+    memcpy(A, A_start, sizeof(A));
+    if (s3d_ref_pass(&c, 0, A_start, raw, S_start)) goto dev_failed;
+    if (!(S_start[73] > 0.0)) {
+        s3d_api_set_error("sift3d_amd_refine_affine: the volumes do not overlap under the transform as given");
+        goto done;
+    }
+    int iters = 0, levels_run = 0;
+    for (int l = c.nlv - 1; l >= 1; l--) {                  /* the coarse levels; one that has no overlap is left out */
+        if (s3d_ref_constants(&c, l, affine, A, normalize, K)) goto done;
+        if (s3d_ref_pass(&c, l, A, K, S)) goto dev_failed;
+        if (!(S[73] > 0.0)) continue;
+        if (s3d_ref_run_level(&c, l, A, K, S, min_overlap * S[73], max_iter, tol, &iters) < 0) goto dev_failed;
+        levels_run++;
+    }
+    if (s3d_ref_constants(&c, 0, affine, A, normalize, K)) goto done;
+    if (normalize && s3d_ref_pass(&c, 0, A_start, K, S_start)) goto dev_failed;
+    const double n_before = S_start[73], cost_before = S_start[72] / S_start[73], n_floor = min_overlap * n_before;
+    memcpy(S, S_start, sizeof(S));
+    if (memcmp(A, A_start, sizeof(A)) != 0) {               /* keep the coarse levels' map only if it is no worse here */
+        if (s3d_ref_pass(&c, 0, A, K, S)) goto dev_failed;
+        if (!(S[73] > 0.0 && S[73] >= n_floor && S[72] / S[73] <= cost_before)) {
+            memcpy(A, A_start, sizeof(A));
+            memcpy(S, S_start, sizeof(S));
+            iters = 0;
+        }
+    }
+    int status = s3d_ref_run_level(&c, 0, A, K, S, n_floor, max_iter, tol, &iters);
+    if (status < 0) goto dev_failed;
+    levels_run++;
+    if (!(S[73] >= n_floor && S[72] / S[73] <= cost_before) || memcmp(A, A_start, sizeof(A)) == 0) {
+        memcpy(A, A_start, sizeof(A));
+        memcpy(S, S_start, sizeof(S));
+        status = SIFT3D_AMD_REFINE_UNCHANGED;
+        iters = 0;
+    }
+    if (status != SIFT3D_AMD_REFINE_UNCHANGED) memcpy(affine->A.u.data_double, A, sizeof(A));
+    if (info != NULL) {
+        info->status = status;
+        info->levels_run = levels_run;
+        info->iters = iters;
+        info->passes = c.passes;
+        info->n_before = (long long)n_before;
+        info->n_after = (long long)S[73];
+        info->cost_before = cost_before;
+        info->cost_after = S[72] / S[73];
+        info->max_corner_shift = s3d_ref_corner_shift(A_start, A, c.lv[0].rd);
+    }
+    rc = SIFT3D_SUCCESS;
+    goto done;
+dev_failed:
+    s3d_api_set_error("sift3d_amd_refine_affine: device failure: %s", s3d_rt_last_error());
+done:
+    s3d_rt_free(d_blk);
+    return rc;
+#undef S3D_REF_VOX
+#undef S3D_REF_ALIGN
+}
+
+int sift3d_amd_refine_affine(const Image *src, const Image *ref, const sift3d_amd_refine_opts *opts, Affine *affine,
+                             sift3d_amd_refine_info *info)
+{
+    if (s3d_refine_check(opts, affine)) return SIFT3D_FAILURE;
+    if (src == NULL || ref == NULL) S3D_REF_FAIL("NULL image");
+    if (src->nc != 1 || ref->nc != 1) S3D_REF_FAIL("single-channel volumes only (nc = %d and %d)", src->nc, ref->nc);
+    if (src->data == NULL || ref->data == NULL) S3D_REF_FAIL("NULL data");
+    if (src->nx < 1 || src->ny < 1 || src->nz < 1 || ref->nx < 1 || ref->ny < 1 || ref->nz < 1) S3D_REF_FAIL("bad dimensions");
+    if (src->nx < 2 || src->ny < 2 || src->nz < 2)
+        S3D_REF_FAIL("a source dimension below 2 has no intensity gradient (%d x %d x %d)", src->nx, src->ny, src->nz);
+    const Image *const ims[2] = {src, ref};
+    float *d_im[2] = {NULL, NULL};
+    int rc = SIFT3D_FAILURE;
+    for (int k = 0; k < 2; k++) {                           /* the device works on default strides */
+        const size_t n = (size_t)ims[k]->nx * ims[k]->ny * ims[k]->nz;
+        const float *h = ims[k]->data;
+        float *packed = NULL;
+        if (!s3d_im_is_default_stride(ims[k])) {
+            if ((packed = (float *)malloc(n * sizeof(float))) == NULL) { s3d_api_set_error("sift3d_amd_refine_affine: out of memory"); goto done; }
+            s3d_im_gather(ims[k], packed);
+            h = packed;
+        }
+        const int dev_rc = s3d_rt_malloc((void **)&d_im[k], n * sizeof(float)) || s3d_rt_h2d(d_im[k], h, n * sizeof(float), NULL) ||
+                           s3d_rt_sync(NULL);
+        free(packed);
+        if (dev_rc) { s3d_api_set_error("sift3d_amd_refine_affine: device failure: %s", s3d_rt_last_error()); goto done; }
+    }
+    rc = sift3d_amd_refine_affine_dev(d_im[0], src->nx, src->ny, src->nz, d_im[1], ref->nx, ref->ny, ref->nz, opts, affine, info, NULL);
+done:
+    s3d_rt_free(d_im[0]); s3d_rt_free(d_im[1]);
+    return rc;
+}

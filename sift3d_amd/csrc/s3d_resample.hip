@@ -544,3 +544,145 @@ extern "C" int s3d_k_minmax_finite(const float *d_v, size_t n, float *d_minmax, 
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }
+
+/* ---- normal equations of one Gauss-Newton step of an intensity-based affine fit (sift3d_amd_refine_affine) ------------------
+ * The similarity pass once more -- every reference voxel through the affine map, the source sampled there -- accumulating the 74
+ * sums of s3d_k_affine_normal_eq (include/s3d_device.h: the terms, their operation order and the index layout) instead of the
+ * histogram.  The coordinates come from s3d_affine_xyz and the sample b from s3d_sample_store, so a voxel's (a, b) and its overlap
+ * are the similarity pass's; the gradient of the tri-linear interpolant is taken on the cell [X0, X0 + 1] x [Y0, Y0 + 1] x
+ * [Z0, Z0 + 1], X0 = min(floor(tx), snx - 2), which is the sampled cell except on the last plane of an axis, where it is the
+ * cell below (a one-sided derivative; the launcher refuses a source dimension < 2).
+ *
+ * Workgroups are persistent as in k_similarity: workgroup g walks the rows g, g + G, .., 256 x-consecutive voxels at a time,
+ * G = s3d_neq_grid(rows, rnx), a function of the dimensions alone.  A thread keeps the 74 sums in registers (148 VGPRs; the
+ * kernel runs at the occupancy that leaves, no private segment: DESIGN.md), then the wave by shuffles, the four waves through
+ * LDS in wave order, the workgroup's partials to its own slot of the scratch, and k_neq_finish adds the slots in a fixed order
+ * (workgroup k of 74, lane l takes slots l, l + 64, .., then the same shuffle tree).  No floating-point atomics.  The count is
+ * carried as a sum of 1.0: integer-valued doubles below 2^53 add exactly in any order.  Every product below is its own rounded
+ * f64 operation (the file is compiled without contraction), so a term is the same f64 here and under the emulator. */
+#define S3D_NEQ_NSUM S3D_NEQ_SUMS
+#define S3D_NEQ_WG_PER_CU 2                                 /* resident workgroups per compute unit at the kernel's registers */
+struct NeqConst { double cx, cy, cz, sa, ma, sb, mb; };
+
+__device__ __forceinline__ bool s3d_finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }   /* false for NaN */
+
+/* workgroups of a normal-equation launch: what is resident on S3D_SIM_CUS compute units, no more than there are rows and no
+ * more than give every workgroup S3D_SIM_MIN_VOX voxels (its 74 sums are reduced once) */
+static unsigned s3d_neq_grid(size_t rows, size_t rnx)
+{
+    size_t g = (size_t)S3D_SIM_CUS * S3D_NEQ_WG_PER_CU;
+    const size_t by_work = (rows * rnx + S3D_SIM_MIN_VOX - 1) / S3D_SIM_MIN_VOX;
+    if (g > by_work) g = by_work;
+    return (unsigned)(rows < g ? rows : g);
+}
+
+__global__ void __launch_bounds__(256)
+k_affine_normal_eq(const float *__restrict__ src, int snx, int sny, int snz, const float *__restrict__ ref, int rnx, int rny,
+                   uint32_t rows, AffineD A, NeqConst K, double *__restrict__ partials)
+{
+    __shared__ double s_red[4][S3D_NEQ_NSUM];
+    const uint32_t tid = threadIdx.x;
+    const size_t sys = (size_t)snx, szs = (size_t)snx * sny;
+    double sum[S3D_NEQ_NSUM];
+#pragma unroll
+    for (int k = 0; k < S3D_NEQ_NSUM; k++) sum[k] = 0.0;
+    for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const uint32_t z = row / (uint32_t)rny, y = row - z * (uint32_t)rny;
+        const double yd = (double)y, zd = (double)z;
+        const double qy = yd - K.cy, qz = zd - K.cz;
+        for (int x0 = 0; x0 < rnx; x0 += 256) {
+            const int x = x0 + (int)tid;
+            const double xd = (double)x;
+            double tx, ty, tz;
+            s3d_affine_xyz(A, xd, yd, zd, tx, ty, tz);
+            if (!(x < rnx && s3d_sample_inside(snx, sny, snz, tx, ty, tz))) continue;
+            const float a = ref[(size_t)row * rnx + x];
+            float b;
+            s3d_sample_store<0>(src, snx, sny, snz, 1, &b, tx, ty, tz);
+            /* the gradient's cell and the position in it: fx, fy, fz in [0, 1], 1 only on the last plane */
+            int X0 = (int)floor(tx), Y0 = (int)floor(ty), Z0 = (int)floor(tz);
+            X0 = X0 < snx - 2 ? X0 : snx - 2;
+            Y0 = Y0 < sny - 2 ? Y0 : sny - 2;
+            Z0 = Z0 < snz - 2 ? Z0 : snz - 2;
+            const double fx = tx - (double)X0, fy = ty - (double)Y0, fz = tz - (double)Z0;
+            const double ux = 1.0 - fx, uy = 1.0 - fy, uz = 1.0 - fz;
+            const float *p = src + ((size_t)X0 + (size_t)Y0 * sys + (size_t)Z0 * szs);
+            const double c000 = p[0], c100 = p[1], c010 = p[sys], c110 = p[sys + 1];
+            const double c001 = p[szs], c101 = p[szs + 1], c011 = p[szs + sys], c111 = p[szs + sys + 1];
+            double gx = ((c100 - c000) * uy + (c110 - c010) * fy) * uz + ((c101 - c001) * uy + (c111 - c011) * fy) * fz;
+            double gy = ((c010 - c000) * ux + (c110 - c100) * fx) * uz + ((c011 - c001) * ux + (c111 - c101) * fx) * fz;
+            double gz = ((c001 - c000) * ux + (c101 - c100) * fx) * uy + ((c011 - c010) * ux + (c111 - c110) * fx) * fy;
+            gx = K.sb * gx;
+            gy = K.sb * gy;
+            gz = K.sb * gz;
+            if (!(s3d_finite_f(a) && s3d_finite_f(b) && s3d_finite_d(gx) && s3d_finite_d(gy) && s3d_finite_d(gz))) continue;
+            const double r = K.sb * ((double)b - K.mb) - K.sa * ((double)a - K.ma);
+            const double qx = xd - K.cx;
+            const double gg[6] = {gx * gx, gx * gy, gx * gz, gy * gy, gy * gz, gz * gz};
+            const double qq[10] = {qx * qx, qx * qy, qx * qz, qx, qy * qy, qy * qz, qy, qz * qz, qz, 1.0};
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int k = 0; k < 10; k++) sum[i * 10 + k] += gg[i] * qq[k];
+            const double rg[3] = {r * gx, r * gy, r * gz};
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                sum[60 + i * 4 + 0] += rg[i] * qx;
+                sum[60 + i * 4 + 1] += rg[i] * qy;
+                sum[60 + i * 4 + 2] += rg[i] * qz;
+                sum[60 + i * 4 + 3] += rg[i];
+            }
+            sum[72] += r * r;
+            sum[73] += 1.0;
+        }
+    }
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < S3D_NEQ_NSUM; k++) {
+        const double v = s3d_wave_sum_f64(sum[k]);
+        if (lane == 0) s_red[wave][k] = v;
+    }
+    __syncthreads();
+    if (tid < S3D_NEQ_NSUM)
+        partials[(size_t)blockIdx.x * S3D_NEQ_NSUM + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+}
+
+/* sums[k] = the slots' k-th partials, added in a fixed order: workgroup k of 74 (one wave), lane l takes slots l, l + 64, .. */
+__global__ void __launch_bounds__(64)
+k_neq_finish(const double *__restrict__ partials, uint32_t nslots, double *__restrict__ sums)
+{
+    const uint32_t lane = threadIdx.x, k = blockIdx.x;
+    double v = 0.0;
+    for (uint32_t s = lane; s < nslots; s += 64u) v += partials[(size_t)s * S3D_NEQ_NSUM + k];
+    v = s3d_wave_sum_f64(v);
+    if (lane == 0) sums[k] = v;
+}
+
+extern "C" size_t s3d_k_affine_normal_eq_scratch_bytes(int rnx, int rny, int rnz)
+{
+    if (rnx < 1 || rny < 1 || rnz < 1) return 0;
+    return (size_t)s3d_neq_grid((size_t)rny * rnz, (size_t)rnx) * S3D_NEQ_NSUM * sizeof(double);
+}
+
+extern "C" int s3d_k_affine_normal_eq(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                      const double A[12], const double c[3], double sa, double ma, double sb, double mb,
+                                      double *d_sums, void *d_scratch, s3d_stream stream)
+{
+    if (snx < 1 || sny < 1 || snz < 1 || rnx < 1 || rny < 1 || rnz < 1) S3D_FAIL("bad dimensions");
+    if (snx < 2 || sny < 2 || snz < 2) S3D_FAIL("a source dimension below 2 has no intensity gradient");
+    if (d_src == NULL || d_ref == NULL || d_sums == NULL || d_scratch == NULL) S3D_FAIL("missing buffer");
+    if (A == NULL || c == NULL) S3D_FAIL("missing affine matrix or centre");
+    const size_t rows = (size_t)rny * rnz;
+    if (rows > 0x7fffffffu) S3D_FAIL("volume too large for the normal-equation grid");
+    const unsigned grid = s3d_neq_grid(rows, (size_t)rnx);
+    AffineD a;
+    for (int i = 0; i < 12; i++) a.a[i] = A[i];
+    const NeqConst K = {c[0], c[1], c[2], sa, ma, sb, mb};
+    double *part = (double *)d_scratch;
+    hipLaunchKernelGGL(k_affine_normal_eq, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, d_ref, rnx, rny,
+                       (uint32_t)rows, a, K, part);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_neq_finish, dim3(S3D_NEQ_NSUM), dim3(64), 0, (hipStream_t)stream, part, (uint32_t)grid, d_sums);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}

@@ -61,6 +61,10 @@ def bind_extensions(L: C.CDLL) -> None:
         L.sift3d_amd_im_similarity.argtypes = [_vp, P(abi.Image), P(abi.Image), P(abi.SimilarityOpts), P(abi.Similarity), _vp]
         L.sift3d_amd_similarity_dev.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
                                                 P(abi.SimilarityOpts), P(abi.Similarity), _vp, _vp]
+    if hasattr(L, "sift3d_amd_refine_affine"):            # (absent from builds older than the intensity-based refinement)
+        L.sift3d_amd_refine_affine.argtypes = [P(abi.Image), P(abi.Image), P(abi.RefineOpts), P(abi.Affine), P(abi.RefineInfo)]
+        L.sift3d_amd_refine_affine_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                   P(abi.RefineOpts), P(abi.Affine), P(abi.RefineInfo), _vp]
 
 
 class DeviceLib:
@@ -130,6 +134,11 @@ class DeviceLib:
             L.s3d_k_minmax_finite.argtypes = [_vp, C.c_size_t, _vp, _vp]
             L.s3d_k_similarity_set_aggregate.argtypes = [C.c_int]
             L.s3d_k_similarity_set_aggregate.restype = None
+        if hasattr(L, "s3d_k_affine_normal_eq"):          # (absent from builds older than the intensity-based refinement)
+            L.s3d_k_affine_normal_eq_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+            L.s3d_k_affine_normal_eq_scratch_bytes.restype = C.c_size_t
+            L.s3d_k_affine_normal_eq.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double)] + [C.c_double] * 4 + [_vp, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -304,6 +313,28 @@ class DeviceLib:
             _vp(d_src), sdims[0], sdims[1], sdims[2], _vp(d_ref), rdims[0], rdims[1], rdims[2], _vp(d_ctrl), _vp(d_params),
             n_ctrl, interp, bins, ref_lo, ref_scale, src_lo, src_scale, c_ref, c_src, _vp(h), _vp(s), _vp(w), _vp(stream)),
             "s3d_k_similarity_tps"), rdims, bins, stream)
+
+    # --- normal equations of an intensity-based affine fit ---------------------------------------------------
+    def affine_normal_eq(self, d_src: int, sdims, d_ref: int, rdims, A, centre, consts=(1.0, 0.0, 1.0, 0.0),
+                         stream=None) -> np.ndarray:
+        """The 74 float64 sums of s3d_k_affine_normal_eq (layout: include/s3d_device.h) for d_src (sdims = (nx, ny, nz),
+        float32, one channel) sampled at A [x y z 1]^T of every voxel of d_ref (rdims); centre: 3 doubles, consts:
+        (sa, ma, sb, mb)."""
+        nbytes = int(self.L.s3d_k_affine_normal_eq_scratch_bytes(rdims[0], rdims[1], rdims[2]))
+        if nbytes == 0:
+            raise RuntimeError("s3d_k_affine_normal_eq_scratch_bytes: bad dimensions")
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        c = np.ascontiguousarray(centre, np.float64).reshape(3)
+        dp = C.POINTER(C.c_double)
+        d_sums, d_scr = self.malloc(74 * 8), self.malloc(nbytes)
+        try:
+            self.check(self.L.s3d_k_affine_normal_eq(_vp(d_src), sdims[0], sdims[1], sdims[2], _vp(d_ref), rdims[0], rdims[1],
+                                                     rdims[2], a.ctypes.data_as(dp), c.ctypes.data_as(dp), *map(float, consts),
+                                                     _vp(d_sums), _vp(d_scr), _vp(stream)), "s3d_k_affine_normal_eq")
+            return self.download(d_sums, (74,), np.float64, stream)
+        finally:
+            self.free(d_sums)
+            self.free(d_scr)
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
