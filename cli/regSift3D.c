@@ -8,7 +8,9 @@
  * the matches near the affine map (sift3d_amd_register_tps), written by --transform and used by --warped, and
  * [--metrics m.csv] [--metric_bins n]: the similarity of the images before and after (sift3d_amd_im_similarity), and
  * [--refine] [--refine_levels n] [--refine_iter n] [--refine_normalize]: the affine map improved on the voxel intensities
- * (sift3d_amd_refine_affine) before it is written, used by --warped and scored by --metrics,
+ * (sift3d_amd_refine_affine) before it is written, used by --warped and scored by --metrics, and
+ * [--demons] [--demons_levels n] [--demons_iter n] [--demons_sigma s] [--demons_field f.nii]: a dense displacement field on top of
+ * the affine map (sift3d_amd_register_demons), written by --demons_field and used by --warped,
  * linked against libsift3d_amd.so.  Detection, description, matching and the warp run as HIP kernels;
  * RANSAC is host C.  As in the reference, --err_thresh and --num_iter are parsed after the Ransac
  * parameters have been copied into the registration object, so they do not reach the estimator
@@ -86,6 +88,24 @@ static void usage(void)
            " --refine_normalize - Compare z-scored intensities: for images \n"
            "       that differ by a gain and an offset. \n"
            "\n"
+           "Deformable options: \n"
+           " --demons - After the affine fit (and --refine, if given), \n"
+           "       register what is left on the voxel intensities: a dense \n"
+           "       displacement field by Thirion's demons, coarse to fine. \n"
+           "       --warped then warps through the affine map plus the \n"
+           "       field. --transform still writes the affine map. \n"
+           " --demons_levels [value] - Pyramid levels, at least 1. \n"
+           "       (default: %d) \n"
+           " --demons_iter [value] - Largest number of passes per level, \n"
+           "       at least 1. (default: %d) \n"
+           " --demons_sigma [value] - Smoothing of the field per pass, in \n"
+           "       voxels of the level, in the interval [0.5, 8]. \n"
+           "       (default: 1.5) \n"
+           " --demons_field [filename] - The displacement field on the \n"
+           "       reference grid, in source voxels: a 4-D image with the \n"
+           "       x, y and z components as channels. \n"
+           "       Supported file formats: .nii, .nii.gz \n"
+           "\n"
            "Other options: \n"
            " --nn_thresh [value] - Matching threshold on the nearest neighbor \n"
            "       ratio, in the interval (0, 1]. (default: %.2f) \n"
@@ -101,7 +121,8 @@ static void usage(void)
            "	to 1mm slices. \n"
            "\n",
            SIFT3D_AMD_TPS_LAMBDA_DEFAULT, SIFT3D_AMD_TPS_MAX_POINTS_DEFAULT, SIFT3D_AMD_SIMILARITY_BINS_MAX,
-           SIFT3D_AMD_SIMILARITY_BINS_DEFAULT, SIFT3D_AMD_REFINE_LEVELS_DEFAULT, SIFT3D_AMD_REFINE_ITER_DEFAULT, SIFT3D_nn_thresh_default,
+           SIFT3D_AMD_SIMILARITY_BINS_DEFAULT, SIFT3D_AMD_REFINE_LEVELS_DEFAULT, SIFT3D_AMD_REFINE_ITER_DEFAULT,
+           SIFT3D_AMD_DEMONS_LEVELS_DEFAULT, SIFT3D_AMD_DEMONS_ITER_DEFAULT, SIFT3D_nn_thresh_default,
            SIFT3D_err_thresh_default, SIFT3D_num_iter_default);
     print_opts_SIFT3D();
 }
@@ -127,7 +148,8 @@ static void complain_path(const char *what, const char *path)
 int main(int argc, char *argv[])
 {
     enum { MATCHES = 'a', TRANSFORM, WARPED, CONCAT, KEYS, LINES, NN_THRESH, ERR_THRESH, NUM_ITER, TYPE, RESAMPLE, TPS_FIT, TPS_LAMBDA,
-           TPS_THRESH, TPS_MAX_POINTS, METRICS, METRIC_BINS, REFINE, REFINE_LEVELS, REFINE_ITER, REFINE_NORMALIZE };
+           TPS_THRESH, TPS_MAX_POINTS, METRICS, METRIC_BINS, REFINE, REFINE_LEVELS, REFINE_ITER, REFINE_NORMALIZE,
+           DEMONS, DEMONS_LEVELS, DEMONS_ITER, DEMONS_SIGMA, DEMONS_FIELD };
     static const struct option longopts[] = {{"matches", required_argument, NULL, MATCHES},
                                              {"transform", required_argument, NULL, TRANSFORM},
                                              {"warped", required_argument, NULL, WARPED},
@@ -149,6 +171,11 @@ int main(int argc, char *argv[])
                                              {"refine_levels", required_argument, NULL, REFINE_LEVELS},
                                              {"refine_iter", required_argument, NULL, REFINE_ITER},
                                              {"refine_normalize", no_argument, NULL, REFINE_NORMALIZE},
+                                             {"demons", no_argument, NULL, DEMONS},
+                                             {"demons_levels", required_argument, NULL, DEMONS_LEVELS},
+                                             {"demons_iter", required_argument, NULL, DEMONS_ITER},
+                                             {"demons_sigma", required_argument, NULL, DEMONS_SIGMA},
+                                             {"demons_field", required_argument, NULL, DEMONS_FIELD},
                                              {0, 0, 0, 0}};
     Reg_SIFT3D reg;
     SIFT3D sift3d;
@@ -159,10 +186,11 @@ int main(int argc, char *argv[])
     Tps tps;
     sift3d_amd_tps_opts tps_opts = {-1.0, 0.0, 0};     /* the library's defaults */
     const char *match_path = NULL, *tform_path = NULL, *warped_path = NULL, *concat_path = NULL, *keys_path = NULL,
-               *lines_path = NULL, *metrics_path = NULL;
+               *lines_path = NULL, *metrics_path = NULL, *field_path = NULL;
     sift3d_amd_similarity_opts sim_opts = {0, LINEAR, {0.0, 0.0}, {0.0, 0.0}};   /* the library's defaults */
     sift3d_amd_refine_opts refine_opts = {0, 0, 0.0, 0.0, 0};                    /* the library's defaults */
-    int have_match = 0, have_tform = 0, resample = 0, use_tps = 0, refine = 0;
+    sift3d_amd_demons_opts demons_opts = {0, 0, 0.0, 0.0, 0.0, 0.0, 0};          /* the library's defaults */
+    int have_match = 0, have_tform = 0, resample = 0, use_tps = 0, refine = 0, demons = 0;
 
     switch (parse_gnu(argc, argv)) {
     case SIFT3D_HELP: usage(); return 0;
@@ -239,6 +267,20 @@ int main(int argc, char *argv[])
             if (refine_opts.max_iter < 1) { complain("Invalid value for refine_iter."); return 1; }
             break;
         case REFINE_NORMALIZE: refine_opts.normalize = 1; break;
+        case DEMONS: demons = 1; break;
+        case DEMONS_LEVELS:
+            demons_opts.levels = atoi(optarg);
+            if (demons_opts.levels < 1) { complain("Invalid value for demons_levels."); return 1; }
+            break;
+        case DEMONS_ITER:
+            demons_opts.max_iter = atoi(optarg);
+            if (demons_opts.max_iter < 1) { complain("Invalid value for demons_iter."); return 1; }
+            break;
+        case DEMONS_SIGMA:
+            demons_opts.sigma = atof(optarg);
+            if (!(demons_opts.sigma >= 0.5 && demons_opts.sigma <= 8.0)) { complain("Invalid value for demons_sigma."); return 1; }
+            break;
+        case DEMONS_FIELD: field_path = optarg; have_tform = 1; break;
         default: return 1;
         }
     }
@@ -250,6 +292,10 @@ int main(int argc, char *argv[])
     if (metrics_path != NULL && resample) { complain("--metrics cannot be combined with --resample."); return 1; }
     if (refine && resample) { complain("--refine cannot be combined with --resample."); return 1; }
     if (refine && use_tps) { complain("--refine cannot be combined with --tps."); return 1; }
+    if (demons && use_tps) { complain("--demons cannot be combined with --tps."); return 1; }
+    if (demons && resample) { complain("--demons cannot be combined with --resample."); return 1; }
+    if (field_path != NULL && !demons) { complain("--demons_field needs --demons."); return 1; }
+    demons = demons && (warped_path != NULL || field_path != NULL);   /* the field only shows in --warped and --demons_field */
     refine = refine && have_tform;                     /* the refined map only shows in --transform, --warped and --metrics */
     use_tps = use_tps && have_tform;                   /* the spline only shows in --transform, --warped and --metrics */
     if (init_tform(&tform, AFFINE) || init_Tps(&tps, IM_NDIMS, IM_NDIMS + 1)) return 1;
@@ -298,6 +344,17 @@ int main(int argc, char *argv[])
         complain_path("Failed to write the transformation parameters", tform_path);
         return 1;
     }
+    Image field;                                       /* on top of tform_out; --transform and --metrics keep to the affine map */
+    init_im(&field);
+    if (demons) {
+        sift3d_amd_demons_info dinfo;
+        if (sift3d_amd_register_demons(&src, &ref, tform_out, &demons_opts, &field, &dinfo)) {
+            fprintf(stderr, "%s\n", sift3d_amd_last_error());
+            complain("Failed to register the images with a displacement field.");
+            return 1;
+        }
+        if (field_path != NULL && im_write(field_path, &field)) { complain_path("Failed to write the displacement field", field_path); return 1; }
+    }
     if (metrics_path != NULL) {                        /* one row per stage, on the images as read */
         const void *const stages[3] = {NULL, &tform, refine ? (const void *)&refined : (const void *)&tps};
         const int nstages = use_tps || refine ? 3 : 2;
@@ -320,7 +377,11 @@ int main(int argc, char *argv[])
         Image warped;
         init_im(&warped);
         if (im_copy_dims(&ref, &warped)) { complain_bug("Failed to resize the warped image."); return 1; }
-        if (im_inv_transform(tform_out, &src, LINEAR, SIFT3D_FALSE, &warped)) { complain_bug("Failed to warp the source image."); return 1; }
+        if (demons ? sift3d_amd_im_warp_field(tform_out, &field, &src, LINEAR, &warped)
+                   : im_inv_transform(tform_out, &src, LINEAR, SIFT3D_FALSE, &warped)) {
+            complain_bug("Failed to warp the source image.");
+            return 1;
+        }
         if (im_write(warped_path, &warped)) { complain_path("Failed to write the warped image", warped_path); return 1; }
         im_free(&warped);
     }
@@ -353,6 +414,7 @@ int main(int argc, char *argv[])
     cleanup_tform(&tform);
     cleanup_tform(&tps);
     cleanup_tform(&refined);
+    im_free(&field);
     cleanup_Mat_rm(&match_src);
     cleanup_Mat_rm(&match_ref);
     cleanup_Reg_SIFT3D(&reg);

@@ -509,6 +509,50 @@ int s3d_k_affine_normal_eq(const float *d_src, int snx, int sny, int snz, const 
                            const double A[12], const double c[3], double sa, double ma, double sb, double mb, double *d_sums,
                            void *d_scratch, s3d_stream stream);
 
+/* ---- deformable registration (s3d_resample.hip; extension, sift3d_amd_register_demons) --------------------------------------
+ * A displacement field over a reference volume of N = rnx * rny * rnz voxels is PLANAR: component c (0 = x, 1 = y, 2 = z, in
+ * source voxels) of reference voxel i = (z * rny + y) * rnx + x is d_u[c * N + i], 3 N floats.  (A wave then reads and writes 256
+ * contiguous bytes per component, and a component is a one-channel volume to s3d_k_sep_fir's fused path.)
+ *
+ * s3d_k_demons_step: one update of Thirion's demons with the gradient of the moving (source) image.  For every reference voxel
+ * (x, y, z), all in f64, every operation rounded on its own (no contraction), left to right:
+ *   (tx, ty, tz) = (A [x y z 1]^T as s3d_k_inv_affine computes it) + ((double)u_x, (double)u_y, (double)u_z);
+ *   a, b, X0, Y0, Z0, gx, gy, gz (scaled by sb) and r = sb (b - mb) - sa (a - ma) at (tx, ty, tz) exactly as
+ *       s3d_k_affine_normal_eq defines them, and the voxel counts under its rule (the sample inside, a and b finite floats,
+ *       the gradient finite);
+ *   D = ((gx * gx + gy * gy) + gz * gz) + kstep * (r * r);
+ *   if the voxel counts, D > 0 and D is finite:  m = (-r) / D,  d_c = m * g_c,  v_c = (float)((double)u_c + d_c);
+ *   otherwise v_c = u_c, its bits copied, and d_c = 0.
+ * |d| = |r| |g| / (|g|^2 + kstep r^2) <= 1 / (2 sqrt(kstep)) (the arithmetic-geometric mean inequality on the denominator), so
+ * kstep = 1 / (4 max_step^2) bounds an update's length by max_step source voxels.
+ *   d_sums[0] = sum r * r,  [1] = n (a sum of 1.0: exact),  [2] = sum ((d_x * d_x + d_y * d_y) + d_z * d_z), over the counted voxels.
+ * No floating-point atomics: per-workgroup partials in d_scratch, added by a second launch in a fixed order; the grid depends on
+ * the dimensions only, so a call's bits repeat.  d_v may be d_u (a voxel reads only its own entry).  d_scratch:
+ * s3d_k_demons_step_scratch_bytes(..) bytes (0: bad dimensions).  Fails with a message, the outputs untouched, for a dimension
+ * < 1, a source dimension < 2, more than 2^31 - 1 rows (rny * rnz) and NULL pointers. */
+size_t s3d_k_demons_step_scratch_bytes(int rnx, int rny, int rnz);
+int s3d_k_demons_step(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                      const double A[12], const float *d_u, float *d_v, double sa, double ma, double sb, double mb, double kstep,
+                      double *d_sums, void *d_scratch, s3d_stream stream);
+/* d_dst(x, y, z, .) = the s3d_k_inv_affine sample of d_src at A [x y z 1]^T + u(x, y, z), d_u a planar field over the dnx x dny x
+ * dnz output grid: zero outside the source, the NaN rule, both interpolations and any nc as there; bit-identical to
+ * s3d_k_inv_affine where u is zero. */
+int s3d_k_inv_field(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny, int dnz,
+                    const double A[12], const float *d_u, int interp, s3d_stream stream);
+/* A planar field one pyramid level up.  Requires c?? = f?? / 2 (integer division), each >= 1.  Every component of fine voxel
+ * (x, y, z) is (float)(2.0 * (double)b), b the float the tri-linear s3d_k_inv_affine sample stores for the coarse component at
+ * (min(x / 2.0, cnx - 1), min(y / 2.0, cny - 1), min(z / 2.0, cnz - 1)): a displacement in coarse voxels is twice as long in fine
+ * voxels. */
+int s3d_k_field_upsample2(const float *d_coarse, int cnx, int cny, int cnz, float *d_fine, int fnx, int fny, int fnz,
+                          s3d_stream stream);
+/* The lengths of a planar field's entries, m = sqrt((u_x * u_x + u_y * u_y) + u_z * u_z) in f64, entries whose m is not finite
+ * left out: d_partials, S3D_FIELD_NORM_SLOTS x 3 doubles, receives per slot (sum m, the count, max m) of the voxels the slot's
+ * workgroup walked (zeros in the slots not used); the caller adds them in slot order.  Which voxels a slot holds depends on nvox
+ * only, so a call's bits repeat. */
+#define S3D_FIELD_NORM_SLOTS 1024
+int s3d_k_field_norm_slots(void);        /* S3D_FIELD_NORM_SLOTS, for callers that do not read this header */
+int s3d_k_field_norm(const float *d_u, size_t nvox, double *d_partials, s3d_stream stream);
+
 /* ---- matcher (s3d_match.hip; replaces match_desc, sift.c:2892-2969) ------------------------------- */
 /* For each of the `na` query rows (row r = d_a + (d_a_sel ? d_a_sel[r] : r) * a_stride, 768 floats) the
  * smallest and second-smallest f64 sum of squared differences over the nb rows of d_b and the index of

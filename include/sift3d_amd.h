@@ -722,6 +722,73 @@ int sift3d_amd_refine_affine_dev(const float *d_src, int snx, int sny, int snz, 
                                  const sift3d_amd_refine_opts *opts, Affine *affine, sift3d_amd_refine_info *info,
                                  void *hip_stream);
 
+/* ---- deformable registration on the device: demons refinement of an affine map --------------------------------------------
+ * What is left after the affine map -- local deformation -- as a dense displacement field u over the reference volume, from the
+ * voxel intensities: the source is compared at T(x) + u(x), T the affine map as given (NULL: the identity), u in source voxels.
+ * Thirion's demons with the gradient of the moving (source) image, diffusion-regularised: one iteration is one pass over the
+ * reference volume (s3d_k_demons_step, include/s3d_device.h: the update, the cost and the count together) and one Gaussian of
+ * sigma voxels over each component of the field (s3d_k_sep_fir, one channel, unit spacing).  The cost is that of
+ * sift3d_amd_refine_affine, sum r^2 / n over the overlap, r = sb (b - mb) - sa (a - ma).
+ *   Pyramid: the refinement's -- level l is l rounds of (Gaussian of sigma 1 voxel, every second voxel), dimensions n / 2, the
+ *       linear part of T kept and its translation scaled by 2^-l; a level at which a dimension of either volume would fall
+ *       below 16 is skipped, and so is one whose reference is too small for the field's Gaussian (a dimension below
+ *       ceil(3 sigma) + 2).  The field of a level is in that level's voxels.
+ *   Start of a level: the coarsest level starts from the zero field, every finer one from s3d_k_field_upsample2 of the level above.
+ *   Iteration k = 0, 1, .. of a level: (1) s3d_k_demons_step from u into v with kstep = 1 / (4 max_step^2), so no voxel moves
+ *       by more than max_step level voxels in one update; (2) the three sums S are read back, c_k = S[0] / S[1]; (3) each
+ *       component of v is smoothed into u.  The taps are init_Gauss_filter's: half width ceil(3 sigma), tap i =
+ *       (float)exp(-0.5 x^2), x = (i - half width) / (sigma + DBL_EPSILON), divided by their float sum.
+ *   Stopping: a level stops CONVERGED at the first k >= 5 with c_k > (1 - tol) c_(k-5), before that pass's update is applied (u
+ *       stays the field c_k was measured on); MAX_ITER after max_iter passes, each applied.  A level whose first pass counts no
+ *       voxel (S[1] == 0) is left out: its field goes on to the next level as it came.
+ *   normalize = 1: sa, ma, sb, mb as in sift3d_amd_refine_affine -- sift3d_amd_similarity_dev under the level's affine map alone,
+ *       frozen for the level.
+ *   Acceptance: cost_before and n_before are those of a level-0 pass with the zero field (no overlap there is a failure),
+ *       cost_after and n_after those of one more level-0 pass on the final field, both with level 0's constants.  The field is
+ *       returned only if cost_after <= cost_before and n_after >= min_overlap * n_before, and level 0 was not left out;
+ *       otherwise it is returned all zero bits with status UNCHANGED.
+ * field: ref's dimensions and units, nc = 3 (x, y, z displacement in source voxels, channel fastest), resized by the call;
+ * d_field: planar, 3 N floats (include/s3d_device.h).  info (may be NULL): status is the way level 0 ended unless UNCHANGED;
+ * levels_run counts the levels not left out, iters the updates applied and passes every s3d_k_demons_step of the call;
+ * mean_disp and max_disp are the mean and the largest |u| over the returned field's finite entries.
+ * SIFT3D_FAILURE with sift3d_amd_last_error set, *field (d_field) and *info untouched, for: no overlap at the start, nc != 1,
+ * NULL data or field, a source dimension < 2, a reference dimension < ceil(3 sigma) + 2, a transform that is neither NULL nor a
+ * 3-D Affine (a Tps is not supported as the base transform), negative levels or max_iter, a NaN or negative tol or min_overlap,
+ * normalize other than 0 or 1, sigma outside 0.5 .. 8, a max_step that is not positive, and a device failure.  opts NULL: all
+ * defaults.  Device memory of a call is freed before it returns. */
+typedef struct {
+    int levels;          /* 0: 3 */
+    int max_iter;        /* 0: 50 passes per level */
+    double sigma;        /* 0: 1.5 level voxels; allowed 0.5 .. 8 */
+    double max_step;     /* 0: 1.0 level voxel */
+    double tol;          /* 0: 1e-3 */
+    double min_overlap;  /* 0: 0.5 */
+    int normalize;       /* 0: raw SSD.  1: z-scored */
+} sift3d_amd_demons_opts;
+#define SIFT3D_AMD_DEMONS_CONVERGED 0
+#define SIFT3D_AMD_DEMONS_MAX_ITER 1
+#define SIFT3D_AMD_DEMONS_UNCHANGED 3
+typedef struct {
+    int status;                        /* SIFT3D_AMD_DEMONS_*, level 0 */
+    int levels_run, iters, passes;
+    long long n_before, n_after;       /* level 0 */
+    double cost_before, cost_after;    /* level 0, sum r^2 / n */
+    double mean_disp, max_disp;        /* |u| over the field, level-0 voxels */
+} sift3d_amd_demons_info;
+#define SIFT3D_AMD_DEMONS_LEVELS_DEFAULT 3
+#define SIFT3D_AMD_DEMONS_ITER_DEFAULT 50
+/* Host volumes: non-default strides are gathered, both volumes are uploaded, the field is downloaded and interleaved. */
+int sift3d_amd_register_demons(const Image *src, const Image *ref, const void *tform /* NULL or a 3-D Affine */,
+                               const sift3d_amd_demons_opts *opts, Image *field /* out: ref's dims and units, nc = 3 */,
+                               sift3d_amd_demons_info *info);
+/* Device-resident volumes (x fastest, default strides); the work is ordered on hip_stream and has completed on return. */
+int sift3d_amd_register_demons_dev(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                   const void *tform, const sift3d_amd_demons_opts *opts, float *d_field /* planar, 3 * N */,
+                                   sift3d_amd_demons_info *info, void *hip_stream);
+/* im_inv_transform through tform (NULL or a 3-D Affine) plus a field: dst(x) = src sampled at T(x) + field(x).  dst takes the
+ * field's dimensions and units and src's channels; the field (nc = 3) is de-interleaved on upload (s3d_k_inv_field). */
+int sift3d_amd_im_warp_field(const void *tform, const Image *field, const Image *src, interp_type interp, Image *dst);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

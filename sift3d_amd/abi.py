@@ -165,6 +165,24 @@ class RefineInfo(C.Structure):
 REFINE_CONVERGED, REFINE_MAX_ITER, REFINE_STALLED, REFINE_UNCHANGED = 0, 1, 2, 3
 
 
+class DemonsOpts(C.Structure):
+    """``sift3d_amd_demons_opts``; a zero field takes its default (levels 3, max_iter 50, sigma 1.5, max_step 1, tol 1e-3,
+    min_overlap 0.5)."""
+    _fields_ = [("levels", C.c_int), ("max_iter", C.c_int), ("sigma", C.c_double), ("max_step", C.c_double), ("tol", C.c_double),
+                ("min_overlap", C.c_double), ("normalize", C.c_int)]
+
+
+class DemonsInfo(C.Structure):
+    """``sift3d_amd_demons_info``: how sift3d_amd_register_demons ended; costs and counts are level 0's, the displacements
+    those of the returned field."""
+    _fields_ = [("status", C.c_int), ("levels_run", C.c_int), ("iters", C.c_int), ("passes", C.c_int),
+                ("n_before", C.c_longlong), ("n_after", C.c_longlong), ("cost_before", C.c_double),
+                ("cost_after", C.c_double), ("mean_disp", C.c_double), ("max_disp", C.c_double)]
+
+
+DEMONS_CONVERGED, DEMONS_MAX_ITER, DEMONS_UNCHANGED = 0, 1, 3
+
+
 class Reg_SIFT3D(C.Structure):
     _fields_ = [("src_units", C.c_double * 3), ("ref_units", C.c_double * 3), ("sift3d", SIFT3D), ("ran", Ransac),
                 ("desc_src", SIFT3D_Descriptor_store), ("desc_ref", SIFT3D_Descriptor_store), ("match_src", Mat_rm),

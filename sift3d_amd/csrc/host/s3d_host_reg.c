@@ -1355,6 +1355,71 @@ typedef struct {
     void *d_scr, *stream;
 } s3d_ref_ctx;
 
+/* The coarse-to-fine pyramid, shared by the refinement and the demons driver.  s3d_ref_plan_pyramid fills in the levels that
+ * exist -- at most `levels`, none with a source dimension below min_sdim or a reference dimension below min_rdim -- and returns the bytes of device memory
+ * they take at the front of the caller's block: the coarse volumes, then (with more than one level) the two work volumes of
+ * the Gaussian.  s3d_ref_build_pyramid fills them: level l is level l - 1 through init_Gauss_filter's taps at sigma = 1,
+ * every second voxel. */
+#define S3D_REF_VOX(d) ((size_t)(d)[0] * (d)[1] * (d)[2])
+#define S3D_REF_ALIGN(b) (((b) + 255) & ~(size_t)255)
+typedef struct { size_t off[S3D_REF_MAX_LEVELS][2], off_work, nwork; } s3d_ref_plan;
+
+static size_t s3d_ref_plan_pyramid(s3d_ref_ctx *const c, s3d_ref_plan *const plan, const int levels, const int min_sdim, const int min_rdim,
+                                   const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                   void *const stream)
+{
+    size_t bytes = 0;
+    memset(c, 0, sizeof(*c));
+    c->stream = stream;
+    c->lv[0] = (s3d_ref_level){d_src, d_ref, {snx, sny, snz}, {rnx, rny, rnz}};
+    c->nlv = 1;
+    while (c->nlv < levels) {
+        const s3d_ref_level *const p = &c->lv[c->nlv - 1];
+        s3d_ref_level *const n = &c->lv[c->nlv];
+        int small = 0;
+        for (int k = 0; k < 3; k++) {
+            n->sd[k] = p->sd[k] / 2;
+            n->rd[k] = p->rd[k] / 2;
+            small = small || n->sd[k] < min_sdim || n->rd[k] < min_rdim;
+        }
+        if (small) break;                                   /* every coarser level would be smaller still */
+        plan->off[c->nlv][0] = bytes; bytes += S3D_REF_ALIGN(S3D_REF_VOX(n->sd) * sizeof(float));
+        plan->off[c->nlv][1] = bytes; bytes += S3D_REF_ALIGN(S3D_REF_VOX(n->rd) * sizeof(float));
+        c->nlv++;
+    }
+    plan->nwork = S3D_REF_VOX(c->lv[0].sd) > S3D_REF_VOX(c->lv[0].rd) ? S3D_REF_VOX(c->lv[0].sd) : S3D_REF_VOX(c->lv[0].rd);
+    plan->off_work = bytes;
+    if (c->nlv > 1) bytes += 2 * S3D_REF_ALIGN(plan->nwork * sizeof(float));
+    return bytes;
+}
+
+static int s3d_ref_build_pyramid(s3d_ref_ctx *const c, const s3d_ref_plan *const plan, unsigned char *const d_blk)
+{
+    if (c->nlv < 2) return 0;
+    float taps[7], acc = 0;                                 /* init_Gauss_filter at sigma = 1 */
+    for (int i = 0; i < 7; i++) {
+        const double x = ((double)i - 3) / (1.0 + DBL_EPSILON);
+        taps[i] = (float)exp(-0.5 * x * x);
+        acc += taps[i];
+    }
+    for (int i = 0; i < 7; i++) taps[i] /= acc;
+    static const float uf[3] = {1.0f, 1.0f, 1.0f};
+    float *const blur = (float *)(d_blk + plan->off_work);
+    float *const tmp = (float *)(d_blk + plan->off_work + S3D_REF_ALIGN(plan->nwork * sizeof(float)));
+    for (int l = 1; l < c->nlv; l++) {
+        const s3d_ref_level *const p = &c->lv[l - 1];
+        float *const dst[2] = {(float *)(d_blk + plan->off[l][0]), (float *)(d_blk + plan->off[l][1])};
+        if (s3d_k_sep_fir(p->src, blur, tmp, p->sd[0], p->sd[1], p->sd[2], 1, uf, taps, 7, c->stream) ||
+            s3d_k_decimate2(blur, p->sd[0], p->sd[1], p->sd[2], dst[0], c->stream) ||
+            s3d_k_sep_fir(p->ref, blur, tmp, p->rd[0], p->rd[1], p->rd[2], 1, uf, taps, 7, c->stream) ||
+            s3d_k_decimate2(blur, p->rd[0], p->rd[1], p->rd[2], dst[1], c->stream))
+            return -1;
+        c->lv[l].src = dst[0];
+        c->lv[l].ref = dst[1];
+    }
+    return 0;
+}
+
 /* the sums of the level-0 map A0 on level l with the constants K = (sa, ma, sb, mb); -1: device failure */
 static int s3d_ref_pass(s3d_ref_ctx *const c, const int l, const double A0[12], const double K[4], double S[S3D_NEQ_SUMS])
 {
@@ -1506,30 +1571,8 @@ int sift3d_amd_refine_affine_dev(const float *d_src, int snx, int sny, int snz, 
     /* the levels that exist, and one device block for them: the coarse volumes, the two work volumes of the Gaussian, the
      * sums and the partials */
     s3d_ref_ctx c;
-    memset(&c, 0, sizeof(c));
-    c.stream = hip_stream;
-    c.lv[0] = (s3d_ref_level){d_src, d_ref, {snx, sny, snz}, {rnx, rny, rnz}};
-    c.nlv = 1;
-    size_t off[S3D_REF_MAX_LEVELS][2], bytes = 0;
-#define S3D_REF_VOX(d) ((size_t)(d)[0] * (d)[1] * (d)[2])
-#define S3D_REF_ALIGN(b) (((b) + 255) & ~(size_t)255)
-    while (c.nlv < levels) {
-        const s3d_ref_level *const p = &c.lv[c.nlv - 1];
-        s3d_ref_level *const n = &c.lv[c.nlv];
-        int small = 0;
-        for (int k = 0; k < 3; k++) {
-            n->sd[k] = p->sd[k] / 2;
-            n->rd[k] = p->rd[k] / 2;
-            small = small || n->sd[k] < S3D_REF_MIN_DIM || n->rd[k] < S3D_REF_MIN_DIM;
-        }
-        if (small) break;                                   /* every coarser level would be smaller still */
-        off[c.nlv][0] = bytes; bytes += S3D_REF_ALIGN(S3D_REF_VOX(n->sd) * sizeof(float));
-        off[c.nlv][1] = bytes; bytes += S3D_REF_ALIGN(S3D_REF_VOX(n->rd) * sizeof(float));
-        c.nlv++;
-    }
-    const size_t nwork = S3D_REF_VOX(c.lv[0].sd) > S3D_REF_VOX(c.lv[0].rd) ? S3D_REF_VOX(c.lv[0].sd) : S3D_REF_VOX(c.lv[0].rd);
-    const size_t off_work = bytes;
-    if (c.nlv > 1) bytes += 2 * S3D_REF_ALIGN(nwork * sizeof(float));
+    s3d_ref_plan plan;
+    size_t bytes = s3d_ref_plan_pyramid(&c, &plan, levels, S3D_REF_MIN_DIM, S3D_REF_MIN_DIM, d_src, snx, sny, snz, d_ref, rnx, rny, rnz, hip_stream);
     const size_t off_sums = bytes;
     bytes += S3D_REF_ALIGN(S3D_NEQ_SUMS * sizeof(double));
     const size_t off_scr = bytes;
@@ -1539,28 +1582,7 @@ int sift3d_amd_refine_affine_dev(const float *d_src, int snx, int sny, int snz, 
     if (s3d_rt_malloc((void **)&d_blk, bytes)) goto dev_failed;
     c.d_sums = (double *)(d_blk + off_sums);
     c.d_scr = d_blk + off_scr;
-    if (c.nlv > 1) {
-        float taps[7], acc = 0;                             /* init_Gauss_filter at sigma = 1 */
-        for (int i = 0; i < 7; i++) {
-            const double x = ((double)i - 3) / (1.0 + DBL_EPSILON);
-            taps[i] = (float)exp(-0.5 * x * x);
-            acc += taps[i];
-        }
-        for (int i = 0; i < 7; i++) taps[i] /= acc;
-        static const float uf[3] = {1.0f, 1.0f, 1.0f};
-        float *const blur = (float *)(d_blk + off_work), *const tmp = (float *)(d_blk + off_work + S3D_REF_ALIGN(nwork * sizeof(float)));
-        for (int l = 1; l < c.nlv; l++) {
-            const s3d_ref_level *const p = &c.lv[l - 1];
-            float *const dst[2] = {(float *)(d_blk + off[l][0]), (float *)(d_blk + off[l][1])};
-            if (s3d_k_sep_fir(p->src, blur, tmp, p->sd[0], p->sd[1], p->sd[2], 1, uf, taps, 7, hip_stream) ||
-                s3d_k_decimate2(blur, p->sd[0], p->sd[1], p->sd[2], dst[0], hip_stream) ||
-                s3d_k_sep_fir(p->ref, blur, tmp, p->rd[0], p->rd[1], p->rd[2], 1, uf, taps, 7, hip_stream) ||
-                s3d_k_decimate2(blur, p->rd[0], p->rd[1], p->rd[2], dst[1], hip_stream))
-                goto dev_failed;
-            c.lv[l].src = dst[0];
-            c.lv[l].ref = dst[1];
-        }
-    }
+    if (s3d_ref_build_pyramid(&c, &plan, d_blk)) goto dev_failed;
 
     double A_start[12], A[12], K[4], S_start[S3D_NEQ_SUMS], S[S3D_NEQ_SUMS];
     static const double raw[4] = {1.0, 0.0, 1.0, 0.0};
@@ -1619,8 +1641,6 @@ dev_failed:
 done:
     s3d_rt_free(d_blk);
     return rc;
-#undef S3D_REF_VOX
-#undef S3D_REF_ALIGN
 }
 
 int sift3d_amd_refine_affine(const Image *src, const Image *ref, const sift3d_amd_refine_opts *opts, Affine *affine,
@@ -1655,3 +1675,348 @@ done:
     s3d_rt_free(d_im[0]); s3d_rt_free(d_im[1]);
     return rc;
 }
+
+/* ---- deformable registration: demons refinement of an affine map (sift3d_amd.h) ------------------------------------------------
+ * The device makes an update and scores the field it started from in one pass (s3d_k_demons_step) and smooths the result
+ * (s3d_k_sep_fir per component); the schedule -- pyramid, stopping rule, acceptance -- is here.  The pyramid is the refinement's. */
+#define S3D_DEM_FAIL(...) do { s3d_api_set_error("sift3d_amd_register_demons: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+#define S3D_DEM_LAG 5
+
+typedef struct { int levels, max_iter, hw, normalize; double sigma, max_step, tol, min_overlap; } s3d_dem_cfg;
+
+/* what both entry points refuse before anything is allocated; *cfg receives the effective options */
+static int s3d_demons_check(const void *const tform, const sift3d_amd_demons_opts *const o, s3d_dem_cfg *const cfg)
+{
+    if (tform != NULL) {
+        const Affine *const a = (const Affine *)tform;
+        if (tform_get_type(tform) != AFFINE || a->A.num_rows != IM_NDIMS || a->A.num_cols != IM_NDIMS + 1 ||
+            a->A.type != SIFT3D_DOUBLE || a->A.u.data_double == NULL)
+            S3D_DEM_FAIL("the transform must be NULL or a 3-D Affine (a Tps is not supported as the base transform)");
+    }
+    if (o != NULL) {
+        if (o->levels < 0 || o->max_iter < 0) S3D_DEM_FAIL("levels and max_iter must not be negative (%d, %d)", o->levels, o->max_iter);
+        if (!(o->tol >= 0.0) || !(o->min_overlap >= 0.0)) S3D_DEM_FAIL("tol and min_overlap must be numbers >= 0");
+        if (o->normalize != 0 && o->normalize != 1) S3D_DEM_FAIL("normalize must be 0 or 1, not %d", o->normalize);
+        if (o->sigma != 0.0 && !(o->sigma >= 0.5 && o->sigma <= 8.0)) S3D_DEM_FAIL("sigma must be in 0.5 .. 8 (0: 1.5), not %g", o->sigma);
+        if (!(o->max_step >= 0.0) || !(o->max_step <= DBL_MAX)) S3D_DEM_FAIL("max_step must be a positive number (0: 1), not %g", o->max_step);
+    }
+    cfg->levels = o != NULL && o->levels != 0 ? o->levels : SIFT3D_AMD_DEMONS_LEVELS_DEFAULT;
+    if (cfg->levels > S3D_REF_MAX_LEVELS) cfg->levels = S3D_REF_MAX_LEVELS;
+    cfg->max_iter = o != NULL && o->max_iter != 0 ? o->max_iter : SIFT3D_AMD_DEMONS_ITER_DEFAULT;
+    cfg->sigma = o != NULL && o->sigma != 0.0 ? o->sigma : 1.5;
+    cfg->max_step = o != NULL && o->max_step != 0.0 ? o->max_step : 1.0;
+    cfg->tol = o != NULL && o->tol != 0.0 ? o->tol : 1e-3;
+    cfg->min_overlap = o != NULL && o->min_overlap != 0.0 ? o->min_overlap : 0.5;
+    cfg->normalize = o != NULL ? o->normalize : 0;
+    cfg->hw = (int)ceil(cfg->sigma * 3.0);
+    return SIFT3D_SUCCESS;
+}
+
+static int s3d_demons_check_dims(const s3d_dem_cfg *const cfg, int snx, int sny, int snz, int rnx, int rny, int rnz)
+{
+    if (snx < 1 || sny < 1 || snz < 1 || rnx < 1 || rny < 1 || rnz < 1) S3D_DEM_FAIL("bad dimensions");
+    if (snx < 2 || sny < 2 || snz < 2) S3D_DEM_FAIL("a source dimension below 2 has no intensity gradient (%d x %d x %d)", snx, sny, snz);
+    if (rnx < cfg->hw + 2 || rny < cfg->hw + 2 || rnz < cfg->hw + 2)
+        S3D_DEM_FAIL("the reference (%d x %d x %d) is too small for a Gaussian of sigma %g: every dimension must be at least %d", rnx,
+                     rny, rnz, cfg->sigma, cfg->hw + 2);
+    return SIFT3D_SUCCESS;
+}
+
+typedef struct {
+    s3d_ref_ctx c;
+    double kstep, *d_sums;
+    void *d_scr;
+    float *u, *v, *tmp;                                     /* device: the field, the updated field, the Gaussian's scratch */
+    float taps[2 * 24 + 1];                                 /* sigma <= 8 */
+    int width, passes;
+} s3d_dem_ctx;
+
+/* one s3d_k_demons_step on level l from d->u into d->v under the level-0 map A0 and the constants K; S: its three sums */
+static int s3d_dem_pass(s3d_dem_ctx *const d, const int l, const double A0[12], const double K[4], double S[3])
+{
+    const s3d_ref_level *const v = &d->c.lv[l];
+    double A[12];
+    memcpy(A, A0, sizeof(A));
+    for (int i = 0; i < 3; i++) A[i * 4 + 3] = A0[i * 4 + 3] / ldexp(1.0, l);
+    if (s3d_k_demons_step(v->src, v->sd[0], v->sd[1], v->sd[2], v->ref, v->rd[0], v->rd[1], v->rd[2], A, d->u, d->v, K[0], K[1], K[2],
+                          K[3], d->kstep, d->d_sums, d->d_scr, d->c.stream) ||
+        s3d_rt_d2h(S, d->d_sums, 3 * sizeof(double), d->c.stream) || s3d_rt_sync(d->c.stream))
+        return -1;
+    d->passes++;
+    return 0;
+}
+
+/* One level from the field in d->u, which becomes the result.  Returns the status the level ended with, -2 where its first
+ * pass counts no voxel (the level is left out), -1 on a device failure.  *iters grows by the updates applied. */
+static int s3d_dem_run_level(s3d_dem_ctx *const d, const int l, const double A0[12], const double K[4], const int max_iter,
+                             const double tol, int *const iters)
+{
+    static const float uf[3] = {1.0f, 1.0f, 1.0f};
+    const s3d_ref_level *const lv = &d->c.lv[l];
+    const size_t n = S3D_REF_VOX(lv->rd);
+    double hist[S3D_DEM_LAG], S[3];
+    for (int k = 0; k < max_iter; k++) {
+        if (s3d_dem_pass(d, l, A0, K, S)) return -1;
+        if (k == 0 && !(S[1] > 0.0)) return -2;
+        const double c = S[0] / S[1];
+        if (k >= S3D_DEM_LAG && c > (1.0 - tol) * hist[k % S3D_DEM_LAG]) return SIFT3D_AMD_DEMONS_CONVERGED;
+        hist[k % S3D_DEM_LAG] = c;
+        for (int comp = 0; comp < 3; comp++)
+            if (s3d_k_sep_fir(d->v + comp * n, d->u + comp * n, d->tmp, lv->rd[0], lv->rd[1], lv->rd[2], 1, uf, d->taps, d->width,
+                              d->c.stream))
+                return -1;
+        (*iters)++;
+    }
+    return SIFT3D_AMD_DEMONS_MAX_ITER;
+}
+
+/* Both entry points behind their checks.  The field goes to d_field (device, planar) and h_field (host, planar), either of
+ * which may be NULL. */
+static int s3d_demons_run(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                          const void *const tform, const s3d_dem_cfg *const cfg, float *const d_field, float *const h_field,
+                          sift3d_amd_demons_info *const info, void *const hip_stream)
+{
+    s3d_dem_ctx d;
+    s3d_ref_plan plan;
+    memset(&d, 0, sizeof(d));
+    /* the reference of a level must hold the field's Gaussian as well as the refinement's 16 voxels */
+    const int min_rdim = cfg->hw + 2 > S3D_REF_MIN_DIM ? cfg->hw + 2 : S3D_REF_MIN_DIM;
+    size_t bytes = s3d_ref_plan_pyramid(&d.c, &plan, cfg->levels, S3D_REF_MIN_DIM, min_rdim, d_src, snx, sny, snz, d_ref, rnx, rny, rnz, hip_stream);
+    const size_t n0 = S3D_REF_VOX(d.c.lv[0].rd), field_bytes = 3 * n0 * sizeof(float);
+    const size_t off_sums = bytes;
+    bytes += S3D_REF_ALIGN(3 * sizeof(double));
+    const size_t off_scr = bytes;
+    bytes += S3D_REF_ALIGN(s3d_k_demons_step_scratch_bytes(rnx, rny, rnz));   /* the finest level has the most workgroups */
+    const size_t off_u = bytes, off_v = off_u + S3D_REF_ALIGN(field_bytes), off_tmp = off_v + S3D_REF_ALIGN(field_bytes);
+    const size_t off_norm = off_tmp + S3D_REF_ALIGN(n0 * sizeof(float)), norm_bytes = S3D_FIELD_NORM_SLOTS * 3 * sizeof(double);
+    bytes = off_norm + norm_bytes;
+    unsigned char *d_blk = NULL;
+    double *h_norm = NULL;
+    Affine ident;
+    int rc = SIFT3D_FAILURE, have_ident = 0;
+    if (tform == NULL) {                                    /* the identity, as a transform the similarity entry point takes */
+        if (init_Affine(&ident, IM_NDIMS)) { s3d_api_set_error("sift3d_amd_register_demons: out of memory"); return SIFT3D_FAILURE; }
+        have_ident = 1;
+        for (int i = 0; i < 12; i++) ident.A.u.data_double[i] = i % 5 == 0 ? 1.0 : 0.0;
+    }
+    const Affine *const like = tform != NULL ? (const Affine *)tform : &ident;
+    double A[12], K0[4], K[4], S_before[3], S[3];
+    memcpy(A, like->A.u.data_double, sizeof(A));
+    if (s3d_rt_malloc((void **)&d_blk, bytes)) goto dev_failed;
+    d.d_sums = (double *)(d_blk + off_sums);
+    d.d_scr = d_blk + off_scr;
+    d.u = (float *)(d_blk + off_u);
+    d.v = (float *)(d_blk + off_v);
+    d.tmp = (float *)(d_blk + off_tmp);
+    d.kstep = 1.0 / (4.0 * cfg->max_step * cfg->max_step);
+    d.width = 2 * cfg->hw + 1;
+    {
+        float acc = 0;                                      /* init_Gauss_filter at sigma */
+        for (int i = 0; i < d.width; i++) {
+            double x = (double)i - cfg->hw;
+            x /= cfg->sigma + DBL_EPSILON;
+            d.taps[i] = (float)exp(-0.5 * x * x);
+            acc += d.taps[i];
+        }
+        for (int i = 0; i < d.width; i++) d.taps[i] /= acc;
+    }
+    if (s3d_ref_build_pyramid(&d.c, &plan, d_blk)) goto dev_failed;
+
+    /* the start: the zero field at level 0 */
+    if (s3d_ref_constants(&d.c, 0, like, A, cfg->normalize, K0)) goto done;
+    if (s3d_rt_memset(d.u, 0, field_bytes, hip_stream) || s3d_dem_pass(&d, 0, A, K0, S_before)) goto dev_failed;
+    if (!(S_before[1] > 0.0)) {
+        s3d_api_set_error("sift3d_amd_register_demons: the volumes do not overlap under the transform as given");
+        goto done;
+    }
+    int iters = 0, levels_run = 0, status = SIFT3D_AMD_DEMONS_UNCHANGED;
+    for (int l = d.c.nlv - 1; l >= 0; l--) {
+        const s3d_ref_level *const lv = &d.c.lv[l];
+        if (l < d.c.nlv - 1) {                              /* the field of the level above, in this level's voxels */
+            const s3d_ref_level *const up = &d.c.lv[l + 1];
+            if (s3d_k_field_upsample2(d.u, up->rd[0], up->rd[1], up->rd[2], d.v, lv->rd[0], lv->rd[1], lv->rd[2], hip_stream))
+                goto dev_failed;
+            float *const t = d.u;
+            d.u = d.v;
+            d.v = t;
+        }
+        if (l == 0) memcpy(K, K0, sizeof(K));
+        else if (s3d_ref_constants(&d.c, l, like, A, cfg->normalize, K)) goto done;
+        const int st = s3d_dem_run_level(&d, l, A, K, cfg->max_iter, cfg->tol, &iters);
+        if (st == -1) goto dev_failed;
+        if (st == -2) continue;
+        levels_run++;
+        if (l == 0) status = st;
+    }
+    if (s3d_dem_pass(&d, 0, A, K0, S)) goto dev_failed;
+    const double cost_before = S_before[0] / S_before[1];
+    /* (a level 0 that was left out has no status of its own: its field is not returned) */
+    const int accepted = status != SIFT3D_AMD_DEMONS_UNCHANGED && S[1] > 0.0 && S[0] / S[1] <= cost_before && S[1] >= cfg->min_overlap * S_before[1];
+    if (!accepted) {
+        status = SIFT3D_AMD_DEMONS_UNCHANGED;
+        iters = 0;
+        memcpy(S, S_before, sizeof(S));
+        if (s3d_rt_memset(d.u, 0, field_bytes, hip_stream)) goto dev_failed;
+    }
+    /* the returned field, and the lengths of its entries: per-workgroup partials from the device, added here in slot order */
+    if ((h_norm = (double *)malloc(norm_bytes)) == NULL) { s3d_api_set_error("sift3d_amd_register_demons: out of memory"); goto done; }
+    if (s3d_k_field_norm(d.u, n0, (double *)(d_blk + off_norm), hip_stream) ||
+        s3d_rt_d2h(h_norm, d_blk + off_norm, norm_bytes, hip_stream) ||
+        (h_field != NULL && s3d_rt_d2h(h_field, d.u, field_bytes, hip_stream)) ||
+        (d_field != NULL && s3d_rt_d2d(d_field, d.u, field_bytes, hip_stream)) || s3d_rt_sync(hip_stream))
+        goto dev_failed;
+    if (info != NULL) {
+        double sum = 0.0, cnt = 0.0, big = 0.0;
+        for (int k = 0; k < S3D_FIELD_NORM_SLOTS; k++) {
+            sum += h_norm[3 * k];
+            cnt += h_norm[3 * k + 1];
+            if (h_norm[3 * k + 2] > big) big = h_norm[3 * k + 2];
+        }
+        info->status = status;
+        info->levels_run = levels_run;
+        info->iters = iters;
+        info->passes = d.passes;
+        info->n_before = (long long)S_before[1];
+        info->n_after = (long long)S[1];
+        info->cost_before = cost_before;
+        info->cost_after = S[0] / S[1];
+        info->mean_disp = cnt > 0.0 ? sum / cnt : 0.0;
+        info->max_disp = big;
+    }
+    rc = SIFT3D_SUCCESS;
+    goto done;
+dev_failed:
+    s3d_api_set_error("sift3d_amd_register_demons: device failure: %s", s3d_rt_last_error());
+done:
+    s3d_rt_free(d_blk);
+    free(h_norm);
+    if (have_ident) cleanup_tform(&ident);
+    return rc;
+}
+
+int sift3d_amd_register_demons_dev(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                   const void *tform, const sift3d_amd_demons_opts *opts, float *d_field,
+                                   sift3d_amd_demons_info *info, void *hip_stream)
+{
+    s3d_dem_cfg cfg;
+    if (s3d_demons_check(tform, opts, &cfg)) return SIFT3D_FAILURE;
+    if (d_src == NULL || d_ref == NULL) S3D_DEM_FAIL("NULL data");
+    if (d_field == NULL) S3D_DEM_FAIL("NULL field");
+    if (s3d_demons_check_dims(&cfg, snx, sny, snz, rnx, rny, rnz)) return SIFT3D_FAILURE;
+    return s3d_demons_run(d_src, snx, sny, snz, d_ref, rnx, rny, rnz, tform, &cfg, d_field, NULL, info, hip_stream);
+}
+
+/* the volumes of ims (one channel) on the device with default strides; `who` names the caller in a message */
+static int s3d_upload_pair(const Image *const ims[2], float *d_im[2], const char *const who)
+{
+    for (int k = 0; k < 2; k++) {
+        const size_t n = (size_t)ims[k]->nx * ims[k]->ny * ims[k]->nz * ims[k]->nc;
+        const float *h = ims[k]->data;
+        float *packed = NULL;
+        if (!s3d_im_is_default_stride(ims[k])) {
+            if ((packed = (float *)malloc(n * sizeof(float))) == NULL) { s3d_api_set_error("%s: out of memory", who); return -1; }
+            s3d_im_gather(ims[k], packed);
+            h = packed;
+        }
+        const int dev_rc = s3d_rt_malloc((void **)&d_im[k], n * sizeof(float)) || s3d_rt_h2d(d_im[k], h, n * sizeof(float), NULL) ||
+                           s3d_rt_sync(NULL);
+        free(packed);
+        if (dev_rc) { s3d_api_set_error("%s: device failure: %s", who, s3d_rt_last_error()); return -1; }
+    }
+    return 0;
+}
+
+int sift3d_amd_register_demons(const Image *src, const Image *ref, const void *tform, const sift3d_amd_demons_opts *opts,
+                               Image *field, sift3d_amd_demons_info *info)
+{
+    s3d_dem_cfg cfg;
+    if (s3d_demons_check(tform, opts, &cfg)) return SIFT3D_FAILURE;
+    if (src == NULL || ref == NULL) S3D_DEM_FAIL("NULL image");
+    if (field == NULL) S3D_DEM_FAIL("NULL field");
+    if (src->nc != 1 || ref->nc != 1) S3D_DEM_FAIL("single-channel volumes only (nc = %d and %d)", src->nc, ref->nc);
+    if (src->data == NULL || ref->data == NULL) S3D_DEM_FAIL("NULL data");
+    if (s3d_demons_check_dims(&cfg, src->nx, src->ny, src->nz, ref->nx, ref->ny, ref->nz)) return SIFT3D_FAILURE;
+    const Image *const ims[2] = {src, ref};
+    float *d_im[2] = {NULL, NULL};
+    const size_t n = (size_t)ref->nx * ref->ny * ref->nz;
+    float *planar = (float *)malloc(3 * n * sizeof(float)), *fresh = (float *)malloc(3 * n * sizeof(float));
+    sift3d_amd_demons_info got;
+    int rc = SIFT3D_FAILURE;
+    if (planar == NULL || fresh == NULL) { s3d_api_set_error("sift3d_amd_register_demons: out of memory"); goto done; }
+    if (s3d_upload_pair(ims, d_im, "sift3d_amd_register_demons")) goto done;
+    if (s3d_demons_run(d_im[0], src->nx, src->ny, src->nz, d_im[1], ref->nx, ref->ny, ref->nz, tform, &cfg, NULL, planar, &got, NULL))
+        goto done;
+    for (size_t i = 0; i < n; i++)
+        for (int c = 0; c < 3; c++) fresh[3 * i + c] = planar[c * n + i];
+    free(field->data);                                      /* nothing can fail from here on: the field takes the new block */
+    field->data = fresh;
+    fresh = NULL;
+    field->size = 3 * n;
+    field->nx = ref->nx; field->ny = ref->ny; field->nz = ref->nz;
+    field->nc = 3;
+    field->ux = ref->ux; field->uy = ref->uy; field->uz = ref->uz;
+    im_default_stride(field);
+    if (info != NULL) *info = got;
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_rt_free(d_im[0]); s3d_rt_free(d_im[1]);
+    free(planar); free(fresh);
+    return rc;
+}
+
+int sift3d_amd_im_warp_field(const void *tform, const Image *field, const Image *src, interp_type interp, Image *dst)
+{
+#define S3D_WF_FAIL(...) do { s3d_api_set_error("sift3d_amd_im_warp_field: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+    static const double identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    if (tform != NULL) {
+        const Affine *const a = (const Affine *)tform;
+        if (tform_get_type(tform) != AFFINE || a->A.num_rows != IM_NDIMS || a->A.num_cols != IM_NDIMS + 1 ||
+            a->A.type != SIFT3D_DOUBLE || a->A.u.data_double == NULL)
+            S3D_WF_FAIL("the transform must be NULL or a 3-D Affine");
+    }
+    if (interp != LINEAR && interp != LANCZOS2) S3D_WF_FAIL("unrecognized interpolation type %d", (int)interp);
+    if (field == NULL || src == NULL || dst == NULL) S3D_WF_FAIL("NULL image");
+    if (field->data == NULL || src->data == NULL) S3D_WF_FAIL("NULL data");
+    if (field->nc != 3) S3D_WF_FAIL("a field has three channels, not %d", field->nc);
+    if (field->nx < 1 || field->ny < 1 || field->nz < 1 || src->nx < 1 || src->ny < 1 || src->nz < 1 || src->nc < 1)
+        S3D_WF_FAIL("bad dimensions");
+    const double *const A = tform != NULL ? ((const Affine *)tform)->A.u.data_double : identity;
+    const size_t n = (size_t)field->nx * field->ny * field->nz, ns = (size_t)src->nx * src->ny * src->nz * src->nc;
+    const size_t nd = n * (size_t)src->nc;
+    float *planar = (float *)malloc(3 * n * sizeof(float)), *packed = NULL, *d_src = NULL, *d_dst = NULL, *d_u = NULL;
+    int rc = SIFT3D_FAILURE;
+    if (planar == NULL) { s3d_api_set_error("sift3d_amd_im_warp_field: out of memory"); goto done; }
+    for (int z = 0; z < field->nz; z++)                     /* de-interleave (any strides) */
+        for (int y = 0; y < field->ny; y++)
+            for (int x = 0; x < field->nx; x++)
+                for (int c = 0; c < 3; c++)
+                    planar[c * n + ((size_t)z * field->ny + y) * field->nx + x] = SIFT3D_IM_GET_VOX(field, x, y, z, c);
+    const float *h_src = src->data;
+    if (!s3d_im_is_default_stride(src)) {
+        if ((packed = (float *)malloc(ns * sizeof(float))) == NULL) { s3d_api_set_error("sift3d_amd_im_warp_field: out of memory"); goto done; }
+        s3d_im_gather(src, packed);
+        h_src = packed;
+    }
+    dst->nx = field->nx; dst->ny = field->ny; dst->nz = field->nz;
+    dst->nc = src->nc;
+    dst->ux = field->ux; dst->uy = field->uy; dst->uz = field->uz;
+    im_default_stride(dst);
+    if (im_resize(dst)) { s3d_api_set_error("sift3d_amd_im_warp_field: out of memory"); goto done; }
+    if (s3d_rt_malloc((void **)&d_src, ns * sizeof(float)) || s3d_rt_malloc((void **)&d_dst, nd * sizeof(float)) ||
+        s3d_rt_malloc((void **)&d_u, 3 * n * sizeof(float)) || s3d_rt_h2d(d_src, h_src, ns * sizeof(float), NULL) ||
+        s3d_rt_h2d(d_u, planar, 3 * n * sizeof(float), NULL) ||
+        s3d_k_inv_field(d_src, src->nx, src->ny, src->nz, src->nc, d_dst, dst->nx, dst->ny, dst->nz, A, d_u, interp == LINEAR ? 0 : 1,
+                        NULL) ||
+        s3d_rt_d2h(dst->data, d_dst, nd * sizeof(float), NULL) || s3d_rt_sync(NULL)) {
+        s3d_api_set_error("sift3d_amd_im_warp_field: device failure: %s", s3d_rt_last_error());
+        goto done;
+    }
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_rt_free(d_src); s3d_rt_free(d_dst); s3d_rt_free(d_u);
+    free(planar); free(packed);
+    return rc;
+#undef S3D_WF_FAIL
+}
+#undef S3D_REF_VOX
+#undef S3D_REF_ALIGN

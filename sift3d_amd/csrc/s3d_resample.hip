@@ -686,3 +686,270 @@ extern "C" int s3d_k_affine_normal_eq(const float *d_src, int snx, int sny, int 
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }
+
+/* ---- deformable registration: the demons update, the warp through a displacement field, the field one level up -------------
+ * (sift3d_amd_register_demons; include/s3d_device.h has the definitions).  A field is planar: component c of voxel i at
+ * d_u[c * N + i], so a wave reads and writes 256 contiguous bytes per component and a component is a one-channel volume to
+ * s3d_k_sep_fir.
+ *
+ * k_demons_step is k_affine_normal_eq with three sums for 74: the same persistent workgroups over rows, the same sample, cell and
+ * gradient at the voxel's coordinates -- here the affine map plus the voxel's own displacement -- and the same reduction (thread,
+ * wave by shuffles, four waves through LDS in wave order, one slot of partials per workgroup, k_demons_finish in a fixed order).
+ * A voxel reads and writes only its own field entry, so the update may be made in place.  Three sums leave the registers to
+ * the gathers (89 VGPRs, five waves per SIMD, no private segment: DESIGN.md); the grid is what is resident at that. */
+#define S3D_DEM_NSUM 3
+#define S3D_DEM_WG_PER_CU 5                                 /* resident workgroups per compute unit at the kernel's registers */
+struct DemConst { double sa, ma, sb, mb, kstep; };
+
+static unsigned s3d_dem_grid(size_t rows, size_t rnx)
+{
+    size_t g = (size_t)S3D_SIM_CUS * S3D_DEM_WG_PER_CU;
+    const size_t by_work = (rows * rnx + S3D_SIM_MIN_VOX - 1) / S3D_SIM_MIN_VOX;
+    if (g > by_work) g = by_work;
+    return (unsigned)(rows < g ? rows : g);
+}
+
+__global__ void __launch_bounds__(256)
+k_demons_step(const float *__restrict__ src, int snx, int sny, int snz, const float *__restrict__ ref, int rnx, int rny,
+              uint32_t rows, AffineD A, DemConst K, const float *u, float *v, size_t nvox, double *__restrict__ partials)
+{
+    __shared__ double s_red[4][S3D_DEM_NSUM];
+    const uint32_t tid = threadIdx.x;
+    const size_t sys = (size_t)snx, szs = (size_t)snx * sny;
+    double sum_rr = 0.0, sum_n = 0.0, sum_dd = 0.0;
+    for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const uint32_t z = row / (uint32_t)rny, y = row - z * (uint32_t)rny;
+        const double yd = (double)y, zd = (double)z;
+        for (int x0 = 0; x0 < rnx; x0 += 256) {
+            const int x = x0 + (int)tid;
+            if (x >= rnx) continue;
+            const size_t i = (size_t)row * rnx + x;
+            const float u0 = u[i], u1 = u[nvox + i], u2 = u[2 * nvox + i];
+            double tx, ty, tz;
+            s3d_affine_xyz(A, (double)x, yd, zd, tx, ty, tz);
+            tx = tx + (double)u0;
+            ty = ty + (double)u1;
+            tz = tz + (double)u2;
+            bool moved = false;
+            if (s3d_sample_inside(snx, sny, snz, tx, ty, tz)) {
+                const float a = ref[i];
+                float b;
+                s3d_sample_store<0>(src, snx, sny, snz, 1, &b, tx, ty, tz);
+                int X0 = (int)floor(tx), Y0 = (int)floor(ty), Z0 = (int)floor(tz);
+                X0 = X0 < snx - 2 ? X0 : snx - 2;
+                Y0 = Y0 < sny - 2 ? Y0 : sny - 2;
+                Z0 = Z0 < snz - 2 ? Z0 : snz - 2;
+                const double fx = tx - (double)X0, fy = ty - (double)Y0, fz = tz - (double)Z0;
+                const double ux = 1.0 - fx, uy = 1.0 - fy, uz = 1.0 - fz;
+                const float *p = src + ((size_t)X0 + (size_t)Y0 * sys + (size_t)Z0 * szs);
+                const double c000 = p[0], c100 = p[1], c010 = p[sys], c110 = p[sys + 1];
+                const double c001 = p[szs], c101 = p[szs + 1], c011 = p[szs + sys], c111 = p[szs + sys + 1];
+                double gx = ((c100 - c000) * uy + (c110 - c010) * fy) * uz + ((c101 - c001) * uy + (c111 - c011) * fy) * fz;
+                double gy = ((c010 - c000) * ux + (c110 - c100) * fx) * uz + ((c011 - c001) * ux + (c111 - c101) * fx) * fz;
+                double gz = ((c001 - c000) * ux + (c101 - c100) * fx) * uy + ((c011 - c010) * ux + (c111 - c110) * fx) * fy;
+                gx = K.sb * gx;
+                gy = K.sb * gy;
+                gz = K.sb * gz;
+                if (s3d_finite_f(a) && s3d_finite_f(b) && s3d_finite_d(gx) && s3d_finite_d(gy) && s3d_finite_d(gz)) {
+                    const double r = K.sb * ((double)b - K.mb) - K.sa * ((double)a - K.ma);
+                    const double D = ((gx * gx + gy * gy) + gz * gz) + K.kstep * (r * r);
+                    sum_rr += r * r;
+                    sum_n += 1.0;
+                    if (D > 0.0 && s3d_finite_d(D)) {
+                        const double m = (-r) / D;
+                        const double dx = m * gx, dy = m * gy, dz = m * gz;
+                        v[i] = (float)((double)u0 + dx);
+                        v[nvox + i] = (float)((double)u1 + dy);
+                        v[2 * nvox + i] = (float)((double)u2 + dz);
+                        sum_dd += (dx * dx + dy * dy) + dz * dz;
+                        moved = true;
+                    }
+                }
+            }
+            if (!moved && v != u) {                         /* the entry as it is, bit for bit (a NaN keeps its payload) */
+                const s3d_u32a *ub = (const s3d_u32a *)u;
+                s3d_u32a *vb = (s3d_u32a *)v;
+                vb[i] = ub[i];
+                vb[nvox + i] = ub[nvox + i];
+                vb[2 * nvox + i] = ub[2 * nvox + i];
+            }
+        }
+    }
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    const double w0 = s3d_wave_sum_f64(sum_rr), w1 = s3d_wave_sum_f64(sum_n), w2 = s3d_wave_sum_f64(sum_dd);
+    if (lane == 0) {
+        s_red[wave][0] = w0;
+        s_red[wave][1] = w1;
+        s_red[wave][2] = w2;
+    }
+    __syncthreads();
+    if (tid < S3D_DEM_NSUM)
+        partials[(size_t)blockIdx.x * S3D_DEM_NSUM + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+}
+
+/* sums[k] = the slots' k-th partials, added in a fixed order: workgroup k of 3 (one wave), lane l takes slots l, l + 64, .. */
+__global__ void __launch_bounds__(64)
+k_demons_finish(const double *__restrict__ partials, uint32_t nslots, double *__restrict__ sums)
+{
+    const uint32_t lane = threadIdx.x, k = blockIdx.x;
+    double v = 0.0;
+    for (uint32_t s = lane; s < nslots; s += 64u) v += partials[(size_t)s * S3D_DEM_NSUM + k];
+    v = s3d_wave_sum_f64(v);
+    if (lane == 0) sums[k] = v;
+}
+
+extern "C" size_t s3d_k_demons_step_scratch_bytes(int rnx, int rny, int rnz)
+{
+    if (rnx < 1 || rny < 1 || rnz < 1) return 0;
+    return (size_t)s3d_dem_grid((size_t)rny * rnz, (size_t)rnx) * S3D_DEM_NSUM * sizeof(double);
+}
+
+extern "C" int s3d_k_demons_step(const float *d_src, int snx, int sny, int snz, const float *d_ref, int rnx, int rny, int rnz,
+                                 const double A[12], const float *d_u, float *d_v, double sa, double ma, double sb, double mb,
+                                 double kstep, double *d_sums, void *d_scratch, s3d_stream stream)
+{
+    if (snx < 1 || sny < 1 || snz < 1 || rnx < 1 || rny < 1 || rnz < 1) S3D_FAIL("bad dimensions");
+    if (snx < 2 || sny < 2 || snz < 2) S3D_FAIL("a source dimension below 2 has no intensity gradient");
+    if (d_src == NULL || d_ref == NULL || d_u == NULL || d_v == NULL || d_sums == NULL || d_scratch == NULL) S3D_FAIL("missing buffer");
+    if (A == NULL) S3D_FAIL("missing affine matrix");
+    const size_t rows = (size_t)rny * rnz;
+    if (rows > 0x7fffffffu) S3D_FAIL("volume too large for the demons grid");
+    const unsigned grid = s3d_dem_grid(rows, (size_t)rnx);
+    AffineD a;
+    for (int i = 0; i < 12; i++) a.a[i] = A[i];
+    const DemConst K = {sa, ma, sb, mb, kstep};
+    double *part = (double *)d_scratch;
+    hipLaunchKernelGGL(k_demons_step, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, d_ref, rnx, rny,
+                       (uint32_t)rows, a, K, d_u, d_v, rows * (size_t)rnx, part);
+    S3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_demons_finish, dim3(S3D_DEM_NSUM), dim3(64), 0, (hipStream_t)stream, part, (uint32_t)grid, d_sums);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* k_inv_affine with the voxel's displacement added to its coordinates */
+template <int INTERP>
+__global__ void __launch_bounds__(256)
+k_inv_field(const float *__restrict__ src, int snx, int sny, int snz, int nc, float *__restrict__ dst, int dnx, int dny, int dnz,
+            AffineD A, const float *__restrict__ u)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, z = blockIdx.z;
+    if (x >= dnx) return;
+    const size_t nvox = (size_t)dnx * dny * dnz, i = ((size_t)z * dny + y) * dnx + x;
+    double tx, ty, tz;
+    s3d_affine_xyz(A, (double)x, (double)y, (double)z, tx, ty, tz);
+    tx = tx + (double)u[i];
+    ty = ty + (double)u[nvox + i];
+    tz = tz + (double)u[2 * nvox + i];
+    s3d_sample_store<INTERP>(src, snx, sny, snz, nc, dst + i * nc, tx, ty, tz);
+}
+
+extern "C" int s3d_k_inv_field(const float *d_src, int snx, int sny, int snz, int nc, float *d_dst, int dnx, int dny, int dnz,
+                               const double A[12], const float *d_u, int interp, s3d_stream stream)
+{
+    if (snx < 1 || sny < 1 || snz < 1 || nc < 1 || dnx < 1 || dny < 1 || dnz < 1) S3D_FAIL("bad dimensions");
+    if (dny > 65535 || dnz > 65535) S3D_FAIL("volume too large for the resampling grid");
+    if (d_src == NULL || d_dst == NULL || d_u == NULL || A == NULL) S3D_FAIL("missing buffer");
+    AffineD a;
+    for (int i = 0; i < 12; i++) a.a[i] = A[i];
+    const dim3 grid(s3d_div_up(dnx, 256), dny, dnz);
+    if (interp == 0)
+        hipLaunchKernelGGL((k_inv_field<0>), grid, dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, nc, d_dst, dnx, dny,
+                           dnz, a, d_u);
+    else if (interp == 1)
+        hipLaunchKernelGGL((k_inv_field<1>), grid, dim3(256), 0, (hipStream_t)stream, d_src, snx, sny, snz, nc, d_dst, dnx, dny,
+                           dnz, a, d_u);
+    else
+        S3D_FAIL("unrecognized interpolation type");
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* one thread per fine voxel, the three components in turn: the tri-linear sample of the coarse component at half the fine
+ * coordinates (clamped to the last coarse sample, so every coordinate is inside), doubled */
+__global__ void __launch_bounds__(256)
+k_field_upsample2(const float *__restrict__ coarse, int cnx, int cny, int cnz, float *__restrict__ fine, int fnx, int fny, int fnz)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y, z = blockIdx.z;
+    if (x >= fnx) return;
+    const size_t nc = (size_t)cnx * cny * cnz, nf = (size_t)fnx * fny * fnz, i = ((size_t)z * fny + y) * fnx + x;
+    double tx = (double)x / 2.0, ty = (double)y / 2.0, tz = (double)z / 2.0;
+    tx = tx < (double)(cnx - 1) ? tx : (double)(cnx - 1);
+    ty = ty < (double)(cny - 1) ? ty : (double)(cny - 1);
+    tz = tz < (double)(cnz - 1) ? tz : (double)(cnz - 1);
+    for (int c = 0; c < 3; c++) {
+        float b;
+        s3d_sample_store<0>(coarse + c * nc, cnx, cny, cnz, 1, &b, tx, ty, tz);
+        fine[c * nf + i] = (float)(2.0 * (double)b);
+    }
+}
+
+extern "C" int s3d_k_field_upsample2(const float *d_coarse, int cnx, int cny, int cnz, float *d_fine, int fnx, int fny, int fnz,
+                                     s3d_stream stream)
+{
+    if (cnx < 1 || cny < 1 || cnz < 1 || fnx < 1 || fny < 1 || fnz < 1) S3D_FAIL("bad dimensions");
+    if (cnx != fnx / 2 || cny != fny / 2 || cnz != fnz / 2) S3D_FAIL("the coarse dimensions must be half the fine ones (integer division)");
+    if (fny > 65535 || fnz > 65535) S3D_FAIL("volume too large for the resampling grid");
+    if (d_coarse == NULL || d_fine == NULL) S3D_FAIL("missing buffer");
+    hipLaunchKernelGGL(k_field_upsample2, dim3(s3d_div_up(fnx, 256), fny, fnz), dim3(256), 0, (hipStream_t)stream, d_coarse, cnx,
+                       cny, cnz, d_fine, fnx, fny, fnz);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* The length of every entry of a planar field in f64, m = sqrt((x * x + y * y) + z * z); entries whose m is not finite are left
+ * out.  Workgroup g of the fixed grid walks the voxels g * 256 + t, + grid * 256, .. and leaves (sum m, the count, max m) in its
+ * slot; the caller adds the S3D_FIELD_NORM_SLOTS slots (cleared by the call, so the unused ones hold zeros) in slot order.  Which
+ * voxels a thread sees depends on nvox only, so the result repeats. */
+__global__ void __launch_bounds__(256)
+k_field_norm(const float *__restrict__ u, size_t nvox, double *__restrict__ partials)
+{
+    __shared__ double s_red[4][3];
+    const uint32_t tid = threadIdx.x;
+    double sum = 0.0, cnt = 0.0, big = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + tid; i < nvox; i += (size_t)gridDim.x * 256) {
+        const double x = u[i], y = u[nvox + i], z = u[2 * nvox + i];
+        const double m = sqrt((x * x + y * y) + z * z);
+        if (!s3d_finite_d(m)) continue;
+        sum += m;
+        cnt += 1.0;
+        big = m > big ? m : big;
+    }
+    sum = s3d_wave_sum_f64(sum);
+    cnt = s3d_wave_sum_f64(cnt);
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_down(big, d);
+        big = o > big ? o : big;
+    }
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    if (lane == 0) {
+        s_red[wave][0] = sum;
+        s_red[wave][1] = cnt;
+        s_red[wave][2] = big;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double *out = partials + (size_t)blockIdx.x * 3;
+        out[0] = ((s_red[0][0] + s_red[1][0]) + s_red[2][0]) + s_red[3][0];
+        out[1] = ((s_red[0][1] + s_red[1][1]) + s_red[2][1]) + s_red[3][1];
+        double b = s_red[0][2];
+        for (int w = 1; w < 4; w++) b = s_red[w][2] > b ? s_red[w][2] : b;
+        out[2] = b;
+    }
+}
+
+extern "C" int s3d_k_field_norm_slots(void) { return S3D_FIELD_NORM_SLOTS; }
+
+extern "C" int s3d_k_field_norm(const float *d_u, size_t nvox, double *d_partials, s3d_stream stream)
+{
+    if (nvox < 1) S3D_FAIL("bad dimensions");
+    if (d_u == NULL || d_partials == NULL) S3D_FAIL("missing buffer");
+    const size_t blocks = (nvox + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < S3D_FIELD_NORM_SLOTS ? blocks : S3D_FIELD_NORM_SLOTS);
+    S3D_HIP(hipMemsetAsync(d_partials, 0, (size_t)S3D_FIELD_NORM_SLOTS * 3 * sizeof(double), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_field_norm, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_u, nvox, d_partials);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}

@@ -65,6 +65,12 @@ def bind_extensions(L: C.CDLL) -> None:
         L.sift3d_amd_refine_affine.argtypes = [P(abi.Image), P(abi.Image), P(abi.RefineOpts), P(abi.Affine), P(abi.RefineInfo)]
         L.sift3d_amd_refine_affine_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
                                                    P(abi.RefineOpts), P(abi.Affine), P(abi.RefineInfo), _vp]
+    if hasattr(L, "sift3d_amd_register_demons"):          # (absent from builds older than the deformable registration)
+        L.sift3d_amd_register_demons.argtypes = [P(abi.Image), P(abi.Image), _vp, P(abi.DemonsOpts), P(abi.Image),
+                                                 P(abi.DemonsInfo)]
+        L.sift3d_amd_register_demons_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,
+                                                     P(abi.DemonsOpts), _vp, P(abi.DemonsInfo), _vp]
+        L.sift3d_amd_im_warp_field.argtypes = [_vp, P(abi.Image), P(abi.Image), C.c_int, P(abi.Image)]
 
 
 class DeviceLib:
@@ -139,6 +145,15 @@ class DeviceLib:
             L.s3d_k_affine_normal_eq_scratch_bytes.restype = C.c_size_t
             L.s3d_k_affine_normal_eq.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
                                                  C.POINTER(C.c_double), C.POINTER(C.c_double)] + [C.c_double] * 4 + [_vp, _vp, _vp]
+        if hasattr(L, "s3d_k_demons_step"):               # (absent from builds older than the deformable registration)
+            L.s3d_k_demons_step_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+            L.s3d_k_demons_step_scratch_bytes.restype = C.c_size_t
+            L.s3d_k_demons_step.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                            _vp, _vp] + [C.c_double] * 5 + [_vp, _vp, _vp]
+            L.s3d_k_inv_field.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_double), _vp, C.c_int, _vp]
+            L.s3d_k_field_upsample2.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]
+            L.s3d_k_field_norm.argtypes = [_vp, C.c_size_t, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -335,6 +350,54 @@ class DeviceLib:
         finally:
             self.free(d_sums)
             self.free(d_scr)
+
+    # --- deformable registration: fields are planar, component c of voxel i at [c * N + i] -----------------------
+    def demons_step(self, d_src: int, sdims, d_ref: int, rdims, A, d_u: int, d_v: int, consts=(1.0, 0.0, 1.0, 0.0),
+                    kstep: float = 0.25, stream=None) -> np.ndarray:
+        """One demons update of the planar field d_u into d_v (which may be d_u) and the three float64 sums (sum r^2, n,
+        sum |update|^2) of s3d_k_demons_step (include/s3d_device.h); consts: (sa, ma, sb, mb), kstep = 1 / (4 max_step^2)."""
+        nbytes = int(self.L.s3d_k_demons_step_scratch_bytes(rdims[0], rdims[1], rdims[2]))
+        if nbytes == 0:
+            raise RuntimeError("s3d_k_demons_step_scratch_bytes: bad dimensions")
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        d_sums, d_scr = self.malloc(3 * 8), self.malloc(nbytes)
+        try:
+            self.check(self.L.s3d_k_demons_step(_vp(d_src), sdims[0], sdims[1], sdims[2], _vp(d_ref), rdims[0], rdims[1], rdims[2],
+                                                a.ctypes.data_as(C.POINTER(C.c_double)), _vp(d_u), _vp(d_v), *map(float, consts),
+                                                float(kstep), _vp(d_sums), _vp(d_scr), _vp(stream)), "s3d_k_demons_step")
+            return self.download(d_sums, (3,), np.float64, stream)
+        finally:
+            self.free(d_sums)
+            self.free(d_scr)
+
+    def inv_field(self, d_src: int, sdims, nc: int, d_dst: int, ddims, A, d_u: int, interp: int = 0, stream=None) -> None:
+        """d_dst (ddims, nc channels) = d_src (sdims) sampled at A [x y z 1]^T + u of every output voxel, d_u a planar field
+        over ddims (s3d_k_inv_field); interp 0 tri-linear, 1 Lanczos-2."""
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        self.check(self.L.s3d_k_inv_field(_vp(d_src), sdims[0], sdims[1], sdims[2], nc, _vp(d_dst), ddims[0], ddims[1], ddims[2],
+                                          a.ctypes.data_as(C.POINTER(C.c_double)), _vp(d_u), interp, _vp(stream)),
+                   "s3d_k_inv_field")
+
+    def field_upsample2(self, d_coarse: int, cdims, d_fine: int, fdims, stream=None) -> None:
+        """The planar field d_coarse (cdims = fdims // 2) one pyramid level up into d_fine, displacements doubled
+        (s3d_k_field_upsample2)."""
+        self.check(self.L.s3d_k_field_upsample2(_vp(d_coarse), cdims[0], cdims[1], cdims[2], _vp(d_fine), fdims[0], fdims[1],
+                                                fdims[2], _vp(stream)), "s3d_k_field_upsample2")
+
+    def field_norm(self, d_u: int, nvox: int, stream=None) -> tuple:
+        """(sum, count, maximum) of the lengths of the planar field's entries, those that are not finite left out
+        (s3d_k_field_norm; its per-workgroup partials added here in slot order)."""
+        slots = int(self.L.s3d_k_field_norm_slots())
+        d_part = self.malloc(slots * 3 * 8)
+        try:
+            self.check(self.L.s3d_k_field_norm(_vp(d_u), nvox, _vp(d_part), _vp(stream)), "s3d_k_field_norm")
+            part = self.download(d_part, (slots, 3), np.float64, stream)
+        finally:
+            self.free(d_part)
+        total = 0.0
+        for v in part[:, 0]:
+            total += float(v)
+        return total, int(part[:, 1].sum()), float(part[:, 2].max())
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
