@@ -10,7 +10,9 @@
  * [--refine] [--refine_levels n] [--refine_iter n] [--refine_normalize]: the affine map improved on the voxel intensities
  * (sift3d_amd_refine_affine) before it is written, used by --warped and scored by --metrics, and
  * [--demons] [--demons_levels n] [--demons_iter n] [--demons_sigma s] [--demons_field f.nii]: a dense displacement field on top of
- * the affine map (sift3d_amd_register_demons), written by --demons_field and used by --warped,
+ * the affine map (sift3d_amd_register_demons), written by --demons_field and used by --warped, and
+ * [--demons_inverse i.nii] [--demons_jacobian j.nii]: the inverse of that map as a field on the source grid
+ * (sift3d_amd_invert_field) and the determinant of its Jacobian on the reference grid (sift3d_amd_field_jacobian),
  * linked against libsift3d_amd.so.  Detection, description, matching and the warp run as HIP kernels;
  * RANSAC is host C.  As in the reference, --err_thresh and --num_iter are parsed after the Ransac
  * parameters have been copied into the registration object, so they do not reach the estimator
@@ -105,6 +107,15 @@ static void usage(void)
            "       reference grid, in source voxels: a 4-D image with the \n"
            "       x, y and z components as channels. \n"
            "       Supported file formats: .nii, .nii.gz \n"
+           " --demons_inverse [filename] - The inverse of the map, as a \n"
+           "       displacement field on the source grid, in reference \n"
+           "       voxels, on top of the inverse affine map: a 4-D image \n"
+           "       like --demons_field. \n"
+           "       Supported file formats: .nii, .nii.gz \n"
+           " --demons_jacobian [filename] - The determinant of the map's \n"
+           "       Jacobian on the reference grid, in voxel coordinates. \n"
+           "       Values <= 0 mark voxels where the map folds. \n"
+           "       Supported file formats: .nii, .nii.gz \n"
            "\n"
            "Other options: \n"
            " --nn_thresh [value] - Matching threshold on the nearest neighbor \n"
@@ -149,7 +160,7 @@ int main(int argc, char *argv[])
 {
     enum { MATCHES = 'a', TRANSFORM, WARPED, CONCAT, KEYS, LINES, NN_THRESH, ERR_THRESH, NUM_ITER, TYPE, RESAMPLE, TPS_FIT, TPS_LAMBDA,
            TPS_THRESH, TPS_MAX_POINTS, METRICS, METRIC_BINS, REFINE, REFINE_LEVELS, REFINE_ITER, REFINE_NORMALIZE,
-           DEMONS, DEMONS_LEVELS, DEMONS_ITER, DEMONS_SIGMA, DEMONS_FIELD };
+           DEMONS, DEMONS_LEVELS, DEMONS_ITER, DEMONS_SIGMA, DEMONS_FIELD, DEMONS_INVERSE, DEMONS_JACOBIAN };
     static const struct option longopts[] = {{"matches", required_argument, NULL, MATCHES},
                                              {"transform", required_argument, NULL, TRANSFORM},
                                              {"warped", required_argument, NULL, WARPED},
@@ -176,6 +187,8 @@ int main(int argc, char *argv[])
                                              {"demons_iter", required_argument, NULL, DEMONS_ITER},
                                              {"demons_sigma", required_argument, NULL, DEMONS_SIGMA},
                                              {"demons_field", required_argument, NULL, DEMONS_FIELD},
+                                             {"demons_inverse", required_argument, NULL, DEMONS_INVERSE},
+                                             {"demons_jacobian", required_argument, NULL, DEMONS_JACOBIAN},
                                              {0, 0, 0, 0}};
     Reg_SIFT3D reg;
     SIFT3D sift3d;
@@ -186,7 +199,7 @@ int main(int argc, char *argv[])
     Tps tps;
     sift3d_amd_tps_opts tps_opts = {-1.0, 0.0, 0};     /* the library's defaults */
     const char *match_path = NULL, *tform_path = NULL, *warped_path = NULL, *concat_path = NULL, *keys_path = NULL,
-               *lines_path = NULL, *metrics_path = NULL, *field_path = NULL;
+               *lines_path = NULL, *metrics_path = NULL, *field_path = NULL, *inverse_path = NULL, *jacobian_path = NULL;
     sift3d_amd_similarity_opts sim_opts = {0, LINEAR, {0.0, 0.0}, {0.0, 0.0}};   /* the library's defaults */
     sift3d_amd_refine_opts refine_opts = {0, 0, 0.0, 0.0, 0};                    /* the library's defaults */
     sift3d_amd_demons_opts demons_opts = {0, 0, 0.0, 0.0, 0.0, 0.0, 0};          /* the library's defaults */
@@ -281,6 +294,8 @@ int main(int argc, char *argv[])
             if (!(demons_opts.sigma >= 0.5 && demons_opts.sigma <= 8.0)) { complain("Invalid value for demons_sigma."); return 1; }
             break;
         case DEMONS_FIELD: field_path = optarg; have_tform = 1; break;
+        case DEMONS_INVERSE: inverse_path = optarg; have_tform = 1; break;
+        case DEMONS_JACOBIAN: jacobian_path = optarg; have_tform = 1; break;
         default: return 1;
         }
     }
@@ -295,7 +310,10 @@ int main(int argc, char *argv[])
     if (demons && use_tps) { complain("--demons cannot be combined with --tps."); return 1; }
     if (demons && resample) { complain("--demons cannot be combined with --resample."); return 1; }
     if (field_path != NULL && !demons) { complain("--demons_field needs --demons."); return 1; }
-    demons = demons && (warped_path != NULL || field_path != NULL);   /* the field only shows in --warped and --demons_field */
+    if (inverse_path != NULL && !demons) { complain("--demons_inverse needs --demons."); return 1; }
+    if (jacobian_path != NULL && !demons) { complain("--demons_jacobian needs --demons."); return 1; }
+    /* the field only shows in --warped and the --demons_.. outputs */
+    demons = demons && (warped_path != NULL || field_path != NULL || inverse_path != NULL || jacobian_path != NULL);
     refine = refine && have_tform;                     /* the refined map only shows in --transform, --warped and --metrics */
     use_tps = use_tps && have_tform;                   /* the spline only shows in --transform, --warped and --metrics */
     if (init_tform(&tform, AFFINE) || init_Tps(&tps, IM_NDIMS, IM_NDIMS + 1)) return 1;
@@ -354,6 +372,29 @@ int main(int argc, char *argv[])
             return 1;
         }
         if (field_path != NULL && im_write(field_path, &field)) { complain_path("Failed to write the displacement field", field_path); return 1; }
+        if (inverse_path != NULL || jacobian_path != NULL) {   /* both are computed, for the line below: they cost a pass each */
+            const double src_units[3] = {src.ux, src.uy, src.uz};
+            sift3d_amd_field_inverse_info iinfo;
+            sift3d_amd_field_jacobian_info jinfo;
+            Affine inv_tform;
+            Image inv_field, det;
+            init_im(&inv_field);
+            init_im(&det);
+            if (init_tform(&inv_tform, AFFINE)) return 1;
+            if (sift3d_amd_invert_field(tform_out, &field, src.nx, src.ny, src.nz, src_units, NULL, &inv_tform, &inv_field, &iinfo) ||
+                sift3d_amd_field_jacobian(tform_out, &field, jacobian_path != NULL ? &det : NULL, &jinfo)) {
+                fprintf(stderr, "%s\n", sift3d_amd_last_error());
+                complain("Failed to invert the displacement field or to map its Jacobian.");
+                return 1;
+            }
+            printf("Deformation: %lld folded voxels of %lld, minimum determinant %g; inverse: %lld converged, %lld not converged "
+                   "of %lld. \n", jinfo.n_folded, jinfo.n, jinfo.min_det, iinfo.n_converged + iinfo.n_outside, iinfo.n_not_converged,
+                   iinfo.n);
+            if (inverse_path != NULL && im_write(inverse_path, &inv_field)) { complain_path("Failed to write the inverse field", inverse_path); return 1; }
+            if (jacobian_path != NULL && im_write(jacobian_path, &det)) { complain_path("Failed to write the determinant map", jacobian_path); return 1; }
+            im_free(&inv_field); im_free(&det);
+            cleanup_tform(&inv_tform);
+        }
     }
     if (metrics_path != NULL) {                        /* one row per stage, on the images as read */
         const void *const stages[3] = {NULL, &tform, refine ? (const void *)&refined : (const void *)&tps};

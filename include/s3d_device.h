@@ -553,6 +553,57 @@ int s3d_k_field_upsample2(const float *d_coarse, int cnx, int cny, int cnz, floa
 int s3d_k_field_norm_slots(void);        /* S3D_FIELD_NORM_SLOTS, for callers that do not read this header */
 int s3d_k_field_norm(const float *d_u, size_t nvox, double *d_partials, s3d_stream stream);
 
+/* ---- the inverse of a field's map and its Jacobian determinant (s3d_resample.hip; sift3d_amd_invert_field, .._field_jacobian) --
+ * The map of a field u over the reference grid is phi(x) = A [x 1]^T + u(x), reference voxel to source voxel coordinates.
+ *
+ * s3d_k_field_invert: the field w over the source grid snx x sny x snz (planar, 3 * snx * sny * snz floats at d_w) with
+ * phi(B [y 1]^T + w(y)) = y, B the inverse of A as the caller computed it, so that (B, w) is itself a map of the kind above,
+ * source voxel to reference voxel.  Per source voxel y = (x, y, z), all in f64, every operation rounded on its own, left to right:
+ *   1. p0 = B [y 1]^T as s3d_k_inv_affine computes it;  w = (+0, +0, +0);  k = 0.
+ *   2. p = p0 + w.  A component of p that is not finite: the voxel is INVALID.
+ *   3. q_a = p_a < 0 ? 0 : p_a > rn_a - 1 ? rn_a - 1 : p_a: the field is continued constantly past its faces.
+ *   4. s_c = the tri-linear s3d_k_inv_affine sample of component c of u at q, as the f64 it is before that kernel rounds it to
+ *      float.  An s_c that is not finite: INVALID.
+ *   5. r_i = ((A[4i] * w_x + A[4i+1] * w_y) + A[4i+2] * w_z) + s_i, which is phi(B y + w) - y in source voxels, and
+ *      e2 = (r_x * r_x + r_y * r_y) + r_z * r_z.  If e2 <= tol * tol (the product rounded once): CONVERGED, w stays.
+ *      Otherwise, if k == max_iter: NOT CONVERGED, w stays.
+ *      Otherwise w_i = -((B[4i] * s_x + B[4i+1] * s_y) + B[4i+2] * s_z), k = k + 1, and again from step 2.
+ *   6. d_w receives (float)w_c; an INVALID voxel the three words 0x7FC00000.
+ *   7. d_status (one byte per source voxel, may be NULL) receives 0: converged and the final p == q, inside the reference grid on
+ *      every axis; 1: converged on the continued field; 2: not converged; 3: invalid.
+ * (The update is the fixed-point form of w = -B u(B y + w); it contracts where |B grad u| < 1, which is also where phi does not
+ * fold.)  u is only read, so a voxel's iteration depends on no other voxel and one launch runs all of them to their end.
+ * d_partials, S3D_FIELD_INV_SLOTS x S3D_FIELD_INV_STATS doubles, cleared by the call, receives per slot: [0 .. 3] the number of
+ * voxels of status 0 .. 3 and [4] the sum of k over all of its voxels (sums of integers in f64: exact), [5] the sum and [6] the
+ * maximum of sqrt(e2) over its voxels of status 0, 1 and 2 (a NaN never becomes the maximum).  The caller adds the slots in slot
+ * order.  Which voxels a slot holds depends on the source dimensions only, and there are no floating-point atomics, so a call's
+ * bits repeat.  A zero field gives all-zero bits and no update.  Fails with a message, the outputs untouched, for a dimension
+ * < 1, NULL d_u, d_w, A, B or d_partials, max_iter < 0, tol negative or NaN, and sny or snz above 65535 (s3d_k_inv_affine's limit). */
+#define S3D_FIELD_INV_SLOTS 2048
+#define S3D_FIELD_INV_STATS 7
+int s3d_k_field_invert_slots(void);      /* the two constants, for callers that do not read this header */
+int s3d_k_field_invert_stats(void);
+int s3d_k_field_invert(const float *d_u, int rnx, int rny, int rnz, const double A[12], const double B[12], float *d_w, int snx,
+                       int sny, int snz, int max_iter, double tol, unsigned char *d_status, double *d_partials, s3d_stream stream);
+/* s3d_k_field_jacobian: det(d phi / d x) per reference voxel.  g_ia, the derivative of component i of u along axis a, is
+ * ((double)u[+1] - (double)u[-1]) * 0.5 away from the faces, (double)u[1] - (double)u[0] at index 0 and (double)u[n-1] -
+ * (double)u[n-2] at index n - 1 of that axis;  J_ia = A[4i+a] + g_ia;
+ *   det = (J00 * (J11 * J22 - J12 * J21) - J01 * (J10 * J22 - J12 * J20)) + J02 * (J10 * J21 - J11 * J20),
+ * every operation a rounded f64 operation, stored as (float)det at d_det (rnx * rny * rnz floats; NULL: statistics only).  The
+ * determinant is in voxel coordinates: the ratio of physical volumes is det times the ratio of the source's voxel volume to the
+ * reference's, a positive factor, so the sign -- det <= 0: the map folds there -- is that of the physical map.
+ * d_partials, S3D_FIELD_JAC_SLOTS x S3D_FIELD_JAC_STATS doubles, cleared by the call, receives per slot over the finite det of
+ * its voxels: [0] their sum, [1] their number, [2] the number of those <= 0, [3] their minimum and [4] their maximum ([3] and [4]
+ * mean something only in a slot whose [1] > 0).  A det that is not finite is stored as computed and left out of all five.  The
+ * caller adds the slots in slot order; the bits repeat as above.  Fails with a message, the outputs untouched, for a dimension
+ * < 2, NULL d_u, A or d_partials, and rny or rnz above 65535. */
+#define S3D_FIELD_JAC_SLOTS 2048
+#define S3D_FIELD_JAC_STATS 5
+int s3d_k_field_jacobian_slots(void);
+int s3d_k_field_jacobian_stats(void);
+int s3d_k_field_jacobian(const float *d_u, int rnx, int rny, int rnz, const double A[12], float *d_det, double *d_partials,
+                         s3d_stream stream);
+
 /* ---- matcher (s3d_match.hip; replaces match_desc, sift.c:2892-2969) ------------------------------- */
 /* For each of the `na` query rows (row r = d_a + (d_a_sel ? d_a_sel[r] : r) * a_stride, 768 floats) the
  * smallest and second-smallest f64 sum of squared differences over the nb rows of d_b and the index of

@@ -789,6 +789,68 @@ int sift3d_amd_register_demons_dev(const float *d_src, int snx, int sny, int snz
  * field's dimensions and units and src's channels; the field (nc = 3) is de-interleaved on upload (s3d_k_inv_field). */
 int sift3d_amd_im_warp_field(const void *tform, const Image *field, const Image *src, interp_type interp, Image *dst);
 
+/* ---- the other direction of a field's map, whether it folds, and points through it ----------------------------------------------
+ * (extension.)  A transform T (NULL: the identity, or a 3-D Affine) and a field u over the reference grid are the map
+ * phi(x) = T(x) + u(x), reference voxel to source voxel coordinates: what sift3d_amd_register_demons returns and
+ * sift3d_amd_im_warp_field takes.
+ *
+ * sift3d_amd_invert_field: psi = phi^-1 over the source grid snx x sny x snz, returned as a pair of the same kind,
+ * psi(y) = inv_tform(y) + inv_field(y), source voxel to reference voxel coordinates.  So sift3d_amd_im_warp_field(&inv_tform,
+ * &inv_field, ref, ..) pulls the reference (an atlas, a label volume) onto the source grid, and sift3d_amd_field_apply_points
+ * with the pair carries source-side points into the reference.  inv_tform = T^-1, the 3 x 3 inverse by cofactors on the host;
+ * inv_field by s3d_k_field_invert (include/s3d_device.h: the iteration, its operation order and the status values): per source
+ * voxel the fixed-point iteration w <- -T^-1 u(T^-1 y + w) on the field continued constantly past its faces, at most max_iter
+ * updates, ended when |phi(psi(y)) - y| <= tol source voxels.  It contracts where the map does not fold; where it does not end,
+ * the voxel keeps its last w and is counted.  info: n = n_converged + n_outside + n_not_converged + n_invalid source voxels --
+ * converged with psi(y) inside the reference grid; converged on the continued field (psi(y) outside it: an extrapolation);
+ * not converged; invalid (a coordinate or a sample that is not finite: the voxel's entries are NaN) --, updates the updates made
+ * over all voxels, mean_residual and max_residual |phi(psi(y)) - y| in source voxels over the voxels that are not invalid.
+ * inv_field takes the source dimensions, src_units (NULL: 1, 1, 1) and nc = 3.
+ * SIFT3D_FAILURE with sift3d_amd_last_error() set and every output untouched for: a transform that is neither NULL nor a 3-D
+ * Affine (a Tps is not supported as the base transform), a linear part that is singular or not finite, a field whose nc != 3,
+ * NULL data or outputs, an inv_tform that is not an initialised 3-D Affine, a dimension < 1, negative max_iter, negative or NaN
+ * tol, units that are not positive, and a device failure.  opts NULL: all defaults.  Device memory of a call is freed before it
+ * returns. */
+typedef struct {
+    int max_iter;        /* 0: 30 updates per voxel */
+    double tol;          /* 0: 1e-3 source voxel */
+} sift3d_amd_field_inverse_opts;
+typedef struct {
+    long long n, n_converged, n_outside, n_not_converged, n_invalid, updates;
+    double mean_residual, max_residual;
+} sift3d_amd_field_inverse_info;
+#define SIFT3D_AMD_FIELD_INVERSE_ITER_DEFAULT 30
+/* Host field (nc = 3, any strides): de-interleaved on upload, the inverse field downloaded and interleaved. */
+int sift3d_amd_invert_field(const void *tform /* NULL or a 3-D Affine */, const Image *field, int snx, int sny, int snz,
+                            const double src_units[3] /* NULL: 1, 1, 1 */, const sift3d_amd_field_inverse_opts *opts,
+                            Affine *inv_tform /* out, initialised by the caller */, Image *inv_field /* out: nc = 3 */,
+                            sift3d_amd_field_inverse_info *info /* may be NULL */);
+/* Device-resident planar fields (3 * rnx * rny * rnz floats in, 3 * snx * sny * snz out); no field is copied to the host.  The
+ * work is ordered on hip_stream and has completed on return.  inv_A: T^-1 as 3 x 4 row-major doubles. */
+int sift3d_amd_invert_field_dev(const float *d_field, int rnx, int rny, int rnz, const void *tform, float *d_inv_field, int snx,
+                                int sny, int snz, const sift3d_amd_field_inverse_opts *opts, double inv_A[12] /* out */,
+                                sift3d_amd_field_inverse_info *info, void *hip_stream);
+
+/* sift3d_amd_field_jacobian: the determinant of d phi / d x per reference voxel (s3d_k_field_jacobian: central differences of
+ * the field, one-sided on the faces, plus T's linear part).  det (may be NULL: statistics only) takes the field's dimensions and
+ * units and nc = 1.  info (may be NULL, not both): n voxels, n_finite of them with a finite determinant, n_folded of those with
+ * det <= 0 -- the map is not invertible there --, and the minimum, maximum and mean over the finite ones (NaN when there is
+ * none).  The determinant is in voxel coordinates: the ratio of physical volumes is det times the ratio of the source's voxel
+ * volume to the reference's; the sign, and with it n_folded, is unaffected.  Fails as above, and for a dimension < 2. */
+typedef struct {
+    long long n, n_finite, n_folded;
+    double min_det, max_det, mean_det;
+} sift3d_amd_field_jacobian_info;
+int sift3d_amd_field_jacobian(const void *tform, const Image *field, Image *det /* may be NULL: statistics only */,
+                              sift3d_amd_field_jacobian_info *info /* may be NULL, not both */);
+int sift3d_amd_field_jacobian_dev(const float *d_field, int rnx, int rny, int rnz, const void *tform, float *d_det,
+                                  sift3d_amd_field_jacobian_info *info, void *hip_stream);
+
+/* out(:, j) = T(in(:, j)) + the tri-linear sample of the field at in(:, j) clamped to the grid: in and out 3 x n doubles (out is
+ * resized; it may be in).  On the host, in plain C: the f64 sample expression of s3d_k_field_invert, not rounded to float, so at
+ * an integer point of the grid it is T(x) + (double)u(x) to the bit.  A point with a coordinate that is not finite gives NaN. */
+int sift3d_amd_field_apply_points(const void *tform, const Image *field, const Mat_rm *in, Mat_rm *out);
+
 /* ---- ABI checks (x86-64 SysV; values measured on the compiled reference) ----------- */
 #if defined(__x86_64__) && !defined(SIFT3D_AMD_NO_ABI_ASSERT)
 #define S3D_ABI_SIZE(T, n) _Static_assert(sizeof(T) == (n), "ABI size of " #T)

@@ -183,6 +183,30 @@ class DemonsInfo(C.Structure):
 DEMONS_CONVERGED, DEMONS_MAX_ITER, DEMONS_UNCHANGED = 0, 1, 3
 
 
+class FieldInverseOpts(C.Structure):
+    """``sift3d_amd_field_inverse_opts``; a zero field takes its default (max_iter 30, tol 1e-3 source voxel)."""
+    _fields_ = [("max_iter", C.c_int), ("tol", C.c_double)]
+
+
+class FieldInverseInfo(C.Structure):
+    """``sift3d_amd_field_inverse_info``: the source voxels by how their iteration ended, the updates made, and the residual
+    |phi(psi(y)) - y| in source voxels over the voxels that are not invalid."""
+    _fields_ = [("n", C.c_longlong), ("n_converged", C.c_longlong), ("n_outside", C.c_longlong),
+                ("n_not_converged", C.c_longlong), ("n_invalid", C.c_longlong), ("updates", C.c_longlong),
+                ("mean_residual", C.c_double), ("max_residual", C.c_double)]
+
+
+class FieldJacobianInfo(C.Structure):
+    """``sift3d_amd_field_jacobian_info``: the determinant of the map's Jacobian over the reference voxels; n_folded counts the
+    finite ones <= 0."""
+    _fields_ = [("n", C.c_longlong), ("n_finite", C.c_longlong), ("n_folded", C.c_longlong), ("min_det", C.c_double),
+                ("max_det", C.c_double), ("mean_det", C.c_double)]
+
+
+# s3d_k_field_invert's status byte per source voxel
+FIELD_INV_CONVERGED, FIELD_INV_OUTSIDE, FIELD_INV_NOT_CONVERGED, FIELD_INV_INVALID = 0, 1, 2, 3
+
+
 class Reg_SIFT3D(C.Structure):
     _fields_ = [("src_units", C.c_double * 3), ("ref_units", C.c_double * 3), ("sift3d", SIFT3D), ("ran", Ransac),
                 ("desc_src", SIFT3D_Descriptor_store), ("desc_ref", SIFT3D_Descriptor_store), ("match_src", Mat_rm),

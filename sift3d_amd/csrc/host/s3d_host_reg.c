@@ -2018,5 +2018,343 @@ done:
     return rc;
 #undef S3D_WF_FAIL
 }
+
+/* ---- the inverse of a field's map, its Jacobian determinant and points through it (sift3d_amd.h) ------------------------------
+ * The device inverts (s3d_k_field_invert) and differentiates (s3d_k_field_jacobian); here are the 3 x 3 inverse, the checks, the
+ * sums of the per-workgroup partials in slot order and the layout of the host forms. */
+static const double s3d_identity34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+
+/* NULL or a 3-D Affine with its matrix in place */
+static int s3d_is_affine3_or_null(const void *const tform)
+{
+    if (tform == NULL) return 1;
+    const Affine *const a = (const Affine *)tform;
+    return tform_get_type(tform) == AFFINE && a->A.num_rows == IM_NDIMS && a->A.num_cols == IM_NDIMS + 1 &&
+           a->A.type == SIFT3D_DOUBLE && a->A.u.data_double != NULL;
+}
+
+static const double *s3d_affine34(const void *const tform)
+{
+    return tform != NULL ? ((const Affine *)tform)->A.u.data_double : s3d_identity34;
+}
+
+/* B = A^-1 as a 3 x 4 map, by cofactors; -1 where A's linear part is singular or an entry of A or B is not finite */
+static int s3d_invert_affine34(const double A[12], double B[12])
+{
+    for (int i = 0; i < 12; i++)
+        if (!(fabs(A[i]) <= DBL_MAX)) return -1;
+    const double c00 = A[5] * A[10] - A[6] * A[9], c01 = A[4] * A[10] - A[6] * A[8], c02 = A[4] * A[9] - A[5] * A[8];
+    const double det = A[0] * c00 - A[1] * c01 + A[2] * c02;
+    if (!(fabs(det) > 0.0) || !(fabs(det) <= DBL_MAX)) return -1;
+    B[0] = c00 / det;
+    B[1] = -(A[1] * A[10] - A[2] * A[9]) / det;
+    B[2] = (A[1] * A[6] - A[2] * A[5]) / det;
+    B[4] = -c01 / det;
+    B[5] = (A[0] * A[10] - A[2] * A[8]) / det;
+    B[6] = -(A[0] * A[6] - A[2] * A[4]) / det;
+    B[8] = c02 / det;
+    B[9] = -(A[0] * A[9] - A[1] * A[8]) / det;
+    B[10] = (A[0] * A[5] - A[1] * A[4]) / det;
+    for (int i = 0; i < 3; i++) B[4 * i + 3] = -((B[4 * i] * A[3] + B[4 * i + 1] * A[7]) + B[4 * i + 2] * A[11]);
+    for (int i = 0; i < 12; i++)
+        if (!(fabs(B[i]) <= DBL_MAX)) return -1;
+    return 0;
+}
+
+/* the channels of a field image, any strides, as a planar field */
+static void s3d_field_to_planar(const Image *const field, float *const planar)
+{
+    const size_t n = (size_t)field->nx * field->ny * field->nz;
+    for (int z = 0; z < field->nz; z++)
+        for (int y = 0; y < field->ny; y++)
+            for (int x = 0; x < field->nx; x++)
+                for (int c = 0; c < 3; c++)
+                    planar[c * n + ((size_t)z * field->ny + y) * field->nx + x] = SIFT3D_IM_GET_VOX(field, x, y, z, c);
+}
+
+#define S3D_FI_FAIL(...) do { s3d_api_set_error("sift3d_amd_invert_field: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+
+/* what both forms of the inversion refuse; max_iter, tol: the effective options; A, B: the map and its inverse */
+static int s3d_invert_check(const void *const tform, const sift3d_amd_field_inverse_opts *const o, int rnx, int rny, int rnz, int snx,
+                            int sny, int snz, int *const max_iter, double *const tol, const double **const A, double B[12])
+{
+    if (!s3d_is_affine3_or_null(tform))
+        S3D_FI_FAIL("the transform must be NULL or a 3-D Affine (a Tps is not supported as the base transform)");
+    if (o != NULL) {
+        if (o->max_iter < 0) S3D_FI_FAIL("max_iter must not be negative (%d)", o->max_iter);
+        if (!(o->tol >= 0.0)) S3D_FI_FAIL("tol must be a number >= 0");
+    }
+    if (rnx < 1 || rny < 1 || rnz < 1 || snx < 1 || sny < 1 || snz < 1)
+        S3D_FI_FAIL("bad dimensions (field %d x %d x %d, source grid %d x %d x %d)", rnx, rny, rnz, snx, sny, snz);
+    *max_iter = o != NULL && o->max_iter != 0 ? o->max_iter : SIFT3D_AMD_FIELD_INVERSE_ITER_DEFAULT;
+    *tol = o != NULL && o->tol != 0.0 ? o->tol : 1e-3;
+    *A = s3d_affine34(tform);
+    if (s3d_invert_affine34(*A, B)) S3D_FI_FAIL("the transform's linear part is singular or not finite: the map has no inverse");
+    return SIFT3D_SUCCESS;
+}
+
+/* the inversion behind its checks: the inverse field to d_w (device, planar), the statistics to *info */
+static int s3d_invert_run(const float *d_u, int rnx, int rny, int rnz, const double A[12], const double B[12], float *d_w, int snx,
+                          int sny, int snz, int max_iter, double tol, sift3d_amd_field_inverse_info *const info, void *const hip_stream)
+{
+    const size_t part_bytes = (size_t)S3D_FIELD_INV_SLOTS * S3D_FIELD_INV_STATS * sizeof(double);
+    double *d_part = NULL, *h_part = (double *)malloc(part_bytes);
+    int rc = SIFT3D_FAILURE;
+    if (h_part == NULL) { s3d_api_set_error("sift3d_amd_invert_field: out of memory"); goto done; }
+    if (s3d_rt_malloc((void **)&d_part, part_bytes) ||
+        s3d_k_field_invert(d_u, rnx, rny, rnz, A, B, d_w, snx, sny, snz, max_iter, tol, NULL, d_part, hip_stream) ||
+        s3d_rt_d2h(h_part, d_part, part_bytes, hip_stream) || s3d_rt_sync(hip_stream)) {
+        s3d_api_set_error("sift3d_amd_invert_field: device failure: %s", s3d_rt_last_error());
+        goto done;
+    }
+    if (info != NULL) {
+        double s[S3D_FIELD_INV_STATS] = {0};
+        for (int k = 0; k < S3D_FIELD_INV_SLOTS; k++) {
+            const double *const p = h_part + (size_t)k * S3D_FIELD_INV_STATS;
+            for (int j = 0; j < 6; j++) s[j] += p[j];
+            if (p[6] > s[6]) s[6] = p[6];
+        }
+        info->n = (long long)snx * sny * snz;
+        info->n_converged = (long long)s[0];
+        info->n_outside = (long long)s[1];
+        info->n_not_converged = (long long)s[2];
+        info->n_invalid = (long long)s[3];
+        info->updates = (long long)s[4];
+        const double valid = (s[0] + s[1]) + s[2];
+        info->mean_residual = valid > 0.0 ? s[5] / valid : 0.0;
+        info->max_residual = s[6];
+    }
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_rt_free(d_part);
+    free(h_part);
+    return rc;
+}
+
+int sift3d_amd_invert_field_dev(const float *d_field, int rnx, int rny, int rnz, const void *tform, float *d_inv_field, int snx,
+                                int sny, int snz, const sift3d_amd_field_inverse_opts *opts, double inv_A[12],
+                                sift3d_amd_field_inverse_info *info, void *hip_stream)
+{
+    int max_iter;
+    double tol, B[12];
+    const double *A;
+    if (d_field == NULL || d_inv_field == NULL) S3D_FI_FAIL("NULL data");
+    if (inv_A == NULL) S3D_FI_FAIL("NULL inverse transform");
+    if (s3d_invert_check(tform, opts, rnx, rny, rnz, snx, sny, snz, &max_iter, &tol, &A, B)) return SIFT3D_FAILURE;
+    sift3d_amd_field_inverse_info got;
+    if (s3d_invert_run(d_field, rnx, rny, rnz, A, B, d_inv_field, snx, sny, snz, max_iter, tol, &got, hip_stream)) return SIFT3D_FAILURE;
+    memcpy(inv_A, B, sizeof(B));
+    if (info != NULL) *info = got;
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_invert_field(const void *tform, const Image *field, int snx, int sny, int snz, const double src_units[3],
+                            const sift3d_amd_field_inverse_opts *opts, Affine *inv_tform, Image *inv_field,
+                            sift3d_amd_field_inverse_info *info)
+{
+    int max_iter;
+    double tol, B[12];
+    const double *A;
+    if (field == NULL || inv_field == NULL) S3D_FI_FAIL("NULL image");
+    if (inv_tform == NULL) S3D_FI_FAIL("NULL inverse transform");
+    if (!s3d_is_affine3_or_null(inv_tform)) S3D_FI_FAIL("the inverse transform must be an initialised 3-D Affine");
+    if (field->data == NULL) S3D_FI_FAIL("NULL data");
+    if (field->nc != 3) S3D_FI_FAIL("a field has three channels, not %d", field->nc);
+    if (src_units != NULL && !(src_units[0] > 0.0 && src_units[1] > 0.0 && src_units[2] > 0.0)) S3D_FI_FAIL("source units must be positive");
+    if (s3d_invert_check(tform, opts, field->nx, field->ny, field->nz, snx, sny, snz, &max_iter, &tol, &A, B)) return SIFT3D_FAILURE;
+    const size_t rn = (size_t)field->nx * field->ny * field->nz, sn = (size_t)snx * sny * snz;
+    float *planar = (float *)malloc(3 * (rn > sn ? rn : sn) * sizeof(float)), *fresh = (float *)malloc(3 * sn * sizeof(float));
+    float *d_u = NULL, *d_w = NULL;
+    sift3d_amd_field_inverse_info got;
+    int rc = SIFT3D_FAILURE;
+    if (planar == NULL || fresh == NULL) { s3d_api_set_error("sift3d_amd_invert_field: out of memory"); goto done; }
+    s3d_field_to_planar(field, planar);
+    if (s3d_rt_malloc((void **)&d_u, 3 * rn * sizeof(float)) || s3d_rt_malloc((void **)&d_w, 3 * sn * sizeof(float)) ||
+        s3d_rt_h2d(d_u, planar, 3 * rn * sizeof(float), NULL) || s3d_rt_sync(NULL)) {
+        s3d_api_set_error("sift3d_amd_invert_field: device failure: %s", s3d_rt_last_error());
+        goto done;
+    }
+    if (s3d_invert_run(d_u, field->nx, field->ny, field->nz, A, B, d_w, snx, sny, snz, max_iter, tol, &got, NULL)) goto done;
+    if (s3d_rt_d2h(planar, d_w, 3 * sn * sizeof(float), NULL) || s3d_rt_sync(NULL)) {
+        s3d_api_set_error("sift3d_amd_invert_field: device failure: %s", s3d_rt_last_error());
+        goto done;
+    }
+    for (size_t i = 0; i < sn; i++)
+        for (int c = 0; c < 3; c++) fresh[3 * i + c] = planar[c * sn + i];
+    free(inv_field->data);                                  /* nothing can fail from here on */
+    inv_field->data = fresh;
+    fresh = NULL;
+    inv_field->size = 3 * sn;
+    inv_field->nx = snx; inv_field->ny = sny; inv_field->nz = snz;
+    inv_field->nc = 3;
+    inv_field->ux = src_units != NULL ? src_units[0] : 1.0;
+    inv_field->uy = src_units != NULL ? src_units[1] : 1.0;
+    inv_field->uz = src_units != NULL ? src_units[2] : 1.0;
+    im_default_stride(inv_field);
+    memcpy(inv_tform->A.u.data_double, B, sizeof(B));
+    if (info != NULL) *info = got;
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_rt_free(d_u); s3d_rt_free(d_w);
+    free(planar); free(fresh);
+    return rc;
+}
+#undef S3D_FI_FAIL
+
+#define S3D_FJ_FAIL(...) do { s3d_api_set_error("sift3d_amd_field_jacobian: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+
+/* the determinant behind its checks: the map to d_det (device, may be NULL), the statistics to *info */
+static int s3d_jacobian_run(const float *d_u, int rnx, int rny, int rnz, const double A[12], float *d_det,
+                            sift3d_amd_field_jacobian_info *const info, void *const hip_stream)
+{
+    const size_t part_bytes = (size_t)S3D_FIELD_JAC_SLOTS * S3D_FIELD_JAC_STATS * sizeof(double);
+    double *d_part = NULL, *h_part = (double *)malloc(part_bytes);
+    int rc = SIFT3D_FAILURE;
+    if (h_part == NULL) { s3d_api_set_error("sift3d_amd_field_jacobian: out of memory"); goto done; }
+    if (s3d_rt_malloc((void **)&d_part, part_bytes) || s3d_k_field_jacobian(d_u, rnx, rny, rnz, A, d_det, d_part, hip_stream) ||
+        s3d_rt_d2h(h_part, d_part, part_bytes, hip_stream) || s3d_rt_sync(hip_stream)) {
+        s3d_api_set_error("sift3d_amd_field_jacobian: device failure: %s", s3d_rt_last_error());
+        goto done;
+    }
+    if (info != NULL) {
+        double sum = 0.0, cnt = 0.0, fold = 0.0, lo = 0.0, hi = 0.0;
+        for (int k = 0; k < S3D_FIELD_JAC_SLOTS; k++) {
+            const double *const p = h_part + (size_t)k * S3D_FIELD_JAC_STATS;
+            if (!(p[1] > 0.0)) continue;
+            if (!(cnt > 0.0) || p[3] < lo) lo = p[3];
+            if (!(cnt > 0.0) || p[4] > hi) hi = p[4];
+            sum += p[0];
+            cnt += p[1];
+            fold += p[2];
+        }
+        info->n = (long long)rnx * rny * rnz;
+        info->n_finite = (long long)cnt;
+        info->n_folded = (long long)fold;
+        info->min_det = cnt > 0.0 ? lo : NAN;
+        info->max_det = cnt > 0.0 ? hi : NAN;
+        info->mean_det = cnt > 0.0 ? sum / cnt : NAN;
+    }
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_rt_free(d_part);
+    free(h_part);
+    return rc;
+}
+
+static int s3d_jacobian_check(const void *const tform, int rnx, int rny, int rnz)
+{
+    if (!s3d_is_affine3_or_null(tform))
+        S3D_FJ_FAIL("the transform must be NULL or a 3-D Affine (a Tps is not supported as the base transform)");
+    if (rnx < 2 || rny < 2 || rnz < 2) S3D_FJ_FAIL("every dimension must be at least 2 (%d x %d x %d)", rnx, rny, rnz);
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_field_jacobian_dev(const float *d_field, int rnx, int rny, int rnz, const void *tform, float *d_det,
+                                  sift3d_amd_field_jacobian_info *info, void *hip_stream)
+{
+    if (d_field == NULL) S3D_FJ_FAIL("NULL data");
+    if (d_det == NULL && info == NULL) S3D_FJ_FAIL("neither a determinant map nor statistics asked for");
+    if (s3d_jacobian_check(tform, rnx, rny, rnz)) return SIFT3D_FAILURE;
+    sift3d_amd_field_jacobian_info got;
+    if (s3d_jacobian_run(d_field, rnx, rny, rnz, s3d_affine34(tform), d_det, &got, hip_stream)) return SIFT3D_FAILURE;
+    if (info != NULL) *info = got;
+    return SIFT3D_SUCCESS;
+}
+
+int sift3d_amd_field_jacobian(const void *tform, const Image *field, Image *det, sift3d_amd_field_jacobian_info *info)
+{
+    if (field == NULL) S3D_FJ_FAIL("NULL image");
+    if (det == NULL && info == NULL) S3D_FJ_FAIL("neither a determinant map nor statistics asked for");
+    if (field->data == NULL) S3D_FJ_FAIL("NULL data");
+    if (field->nc != 3) S3D_FJ_FAIL("a field has three channels, not %d", field->nc);
+    if (s3d_jacobian_check(tform, field->nx, field->ny, field->nz)) return SIFT3D_FAILURE;
+    const size_t n = (size_t)field->nx * field->ny * field->nz;
+    float *planar = (float *)malloc(3 * n * sizeof(float)), *fresh = det != NULL ? (float *)malloc(n * sizeof(float)) : NULL;
+    float *d_u = NULL, *d_det = NULL;
+    sift3d_amd_field_jacobian_info got;
+    int rc = SIFT3D_FAILURE;
+    if (planar == NULL || (det != NULL && fresh == NULL)) { s3d_api_set_error("sift3d_amd_field_jacobian: out of memory"); goto done; }
+    s3d_field_to_planar(field, planar);
+    if (s3d_rt_malloc((void **)&d_u, 3 * n * sizeof(float)) || (det != NULL && s3d_rt_malloc((void **)&d_det, n * sizeof(float))) ||
+        s3d_rt_h2d(d_u, planar, 3 * n * sizeof(float), NULL) || s3d_rt_sync(NULL)) {
+        s3d_api_set_error("sift3d_amd_field_jacobian: device failure: %s", s3d_rt_last_error());
+        goto done;
+    }
+    if (s3d_jacobian_run(d_u, field->nx, field->ny, field->nz, s3d_affine34(tform), d_det, &got, NULL)) goto done;
+    if (det != NULL) {
+        if (s3d_rt_d2h(fresh, d_det, n * sizeof(float), NULL) || s3d_rt_sync(NULL)) {
+            s3d_api_set_error("sift3d_amd_field_jacobian: device failure: %s", s3d_rt_last_error());
+            goto done;
+        }
+        free(det->data);                                    /* nothing can fail from here on */
+        det->data = fresh;
+        fresh = NULL;
+        det->size = n;
+        det->nx = field->nx; det->ny = field->ny; det->nz = field->nz;
+        det->nc = 1;
+        det->ux = field->ux; det->uy = field->uy; det->uz = field->uz;
+        im_default_stride(det);
+    }
+    if (info != NULL) *info = got;
+    rc = SIFT3D_SUCCESS;
+done:
+    s3d_rt_free(d_u); s3d_rt_free(d_det);
+    free(planar); free(fresh);
+    return rc;
+}
+#undef S3D_FJ_FAIL
+
+/* s3d_k_field_invert's steps 3 and 4 on the host, for channel c of a field image: the same expression, the same order */
+static double s3d_field_sample_clamped(const Image *const f, const int c, double tx, double ty, double tz)
+{
+    const double hx = (double)(f->nx - 1), hy = (double)(f->ny - 1), hz = (double)(f->nz - 1);
+    tx = tx < 0.0 ? 0.0 : tx > hx ? hx : tx;
+    ty = ty < 0.0 ? 0.0 : ty > hy ? hy : ty;
+    tz = tz < 0.0 ? 0.0 : tz > hz ? hz : tz;
+    const int fx = (int)floor(tx), fy = (int)floor(ty), fz = (int)floor(tz);
+    const int cx = (int)ceil(tx), cy = (int)ceil(ty), cz = (int)ceil(tz);
+    const double dx = tx - fx, dy = ty - fy, dz = tz - fz;
+    const double c0 = SIFT3D_IM_GET_VOX(f, fx, fy, fz, c), c1 = SIFT3D_IM_GET_VOX(f, fx, cy, fz, c);
+    const double c2 = SIFT3D_IM_GET_VOX(f, cx, fy, fz, c), c3 = SIFT3D_IM_GET_VOX(f, cx, cy, fz, c);
+    const double c4 = SIFT3D_IM_GET_VOX(f, fx, fy, cz, c), c5 = SIFT3D_IM_GET_VOX(f, fx, cy, cz, c);
+    const double c6 = SIFT3D_IM_GET_VOX(f, cx, fy, cz, c), c7 = SIFT3D_IM_GET_VOX(f, cx, cy, cz, c);
+    return c0 * (1.0 - dx) * (1.0 - dy) * (1.0 - dz) + c1 * (1.0 - dx) * dy * (1.0 - dz) +
+           c2 * dx * (1.0 - dy) * (1.0 - dz) + c3 * dx * dy * (1.0 - dz) +
+           c4 * (1.0 - dx) * (1.0 - dy) * dz + c5 * (1.0 - dx) * dy * dz +
+           c6 * dx * (1.0 - dy) * dz + c7 * dx * dy * dz;
+}
+
+int sift3d_amd_field_apply_points(const void *tform, const Image *field, const Mat_rm *in, Mat_rm *out)
+{
+#define S3D_FP_FAIL(...) do { s3d_api_set_error("sift3d_amd_field_apply_points: " __VA_ARGS__); return SIFT3D_FAILURE; } while (0)
+    if (!s3d_is_affine3_or_null(tform))
+        S3D_FP_FAIL("the transform must be NULL or a 3-D Affine (a Tps is not supported as the base transform)");
+    if (field == NULL || in == NULL || out == NULL) S3D_FP_FAIL("NULL argument");
+    if (field->data == NULL) S3D_FP_FAIL("NULL data");
+    if (field->nc != 3) S3D_FP_FAIL("a field has three channels, not %d", field->nc);
+    if (field->nx < 1 || field->ny < 1 || field->nz < 1) S3D_FP_FAIL("bad dimensions");
+    if (in->type != SIFT3D_DOUBLE || in->num_rows != IM_NDIMS || in->num_cols < 0 || (in->num_cols > 0 && in->u.data_double == NULL))
+        S3D_FP_FAIL("the points must be a 3 x n matrix of doubles");
+    const double *const A = s3d_affine34(tform);
+    const size_t n = (size_t)in->num_cols;
+    double *res = NULL;
+    if (n > 0 && (res = (double *)malloc(3 * n * sizeof(double))) == NULL) S3D_FP_FAIL("out of memory");
+    for (size_t j = 0; j < n; j++) {
+        const double x = in->u.data_double[j], y = in->u.data_double[n + j], z = in->u.data_double[2 * n + j];
+        const int ok = fabs(x) <= DBL_MAX && fabs(y) <= DBL_MAX && fabs(z) <= DBL_MAX;     /* a NaN has no cell: NaN out */
+        for (int i = 0; i < 3; i++) {
+            const double t = A[4 * i] * x + A[4 * i + 1] * y + A[4 * i + 2] * z + A[4 * i + 3];
+            res[i * n + j] = ok ? t + s3d_field_sample_clamped(field, i, x, y, z) : NAN;
+        }
+    }
+    out->type = SIFT3D_DOUBLE;
+    out->num_rows = IM_NDIMS;
+    out->num_cols = in->num_cols;
+    if (resize_Mat_rm(out)) { free(res); S3D_FP_FAIL("out of memory"); }
+    if (n > 0) memcpy(out->u.data_double, res, 3 * n * sizeof(double));
+    free(res);
+    return SIFT3D_SUCCESS;
+#undef S3D_FP_FAIL
+}
 #undef S3D_REF_VOX
 #undef S3D_REF_ALIGN

@@ -28,6 +28,24 @@ __device__ __forceinline__ bool s3d_sample_inside(int snx, int sny, int snz, dou
     return !(outside || !(tx == tx) || !(ty == ty) || !(tz == tz));
 }
 
+/* resample_linear's expression at (tx, ty, tz), inside [0, n - 1] on every axis, in f64 before any rounding to float: p the
+ * channel's first element, the strides in floats.  s3d_sample_store<0> stores its float; the field inversion iterates on it. */
+__device__ __forceinline__ double s3d_trilinear_f64(const float *__restrict__ p, size_t sxs, size_t sys, size_t szs, double tx,
+                                                    double ty, double tz)
+{
+    const int fx = (int)floor(tx), fy = (int)floor(ty), fz = (int)floor(tz);
+    const int cx = (int)ceil(tx), cy = (int)ceil(ty), cz = (int)ceil(tz);
+    const double dx = tx - fx, dy = ty - fy, dz = tz - fz;
+    const double c0 = p[fx * sxs + fy * sys + fz * szs], c1 = p[fx * sxs + cy * sys + fz * szs];
+    const double c2 = p[cx * sxs + fy * sys + fz * szs], c3 = p[cx * sxs + cy * sys + fz * szs];
+    const double c4 = p[fx * sxs + fy * sys + cz * szs], c5 = p[fx * sxs + cy * sys + cz * szs];
+    const double c6 = p[cx * sxs + fy * sys + cz * szs], c7 = p[cx * sxs + cy * sys + cz * szs];
+    return c0 * (1.0 - dx) * (1.0 - dy) * (1.0 - dz) + c1 * (1.0 - dx) * dy * (1.0 - dz) +
+           c2 * dx * (1.0 - dy) * (1.0 - dz) + c3 * dx * dy * (1.0 - dz) +
+           c4 * (1.0 - dx) * (1.0 - dy) * dz + c5 * (1.0 - dx) * dy * dz +
+           c6 * dx * (1.0 - dy) * dz + c7 * dx * dy * dz;
+}
+
 /* The sample of src at (tx, ty, tz), every channel, to out[0 .. nc): the reference's resample_linear / resample_lanczos2.
  * Shared by the affine and the spline warp and by the similarity kernels. */
 template <int INTERP>
@@ -40,21 +58,7 @@ __device__ __forceinline__ void s3d_sample_store(const float *__restrict__ src, 
         return;
     }
     if (INTERP == 0) {
-        const int fx = (int)floor(tx), fy = (int)floor(ty), fz = (int)floor(tz);
-        const int cx = (int)ceil(tx), cy = (int)ceil(ty), cz = (int)ceil(tz);
-        const double dx = tx - fx, dy = ty - fy, dz = tz - fz;
-        for (int c = 0; c < nc; c++) {
-            const float *p = src + c;
-            const double c0 = p[fx * sxs + fy * sys + fz * szs], c1 = p[fx * sxs + cy * sys + fz * szs];
-            const double c2 = p[cx * sxs + fy * sys + fz * szs], c3 = p[cx * sxs + cy * sys + fz * szs];
-            const double c4 = p[fx * sxs + fy * sys + cz * szs], c5 = p[fx * sxs + cy * sys + cz * szs];
-            const double c6 = p[cx * sxs + fy * sys + cz * szs], c7 = p[cx * sxs + cy * sys + cz * szs];
-            const double v = c0 * (1.0 - dx) * (1.0 - dy) * (1.0 - dz) + c1 * (1.0 - dx) * dy * (1.0 - dz) +
-                             c2 * dx * (1.0 - dy) * (1.0 - dz) + c3 * dx * dy * (1.0 - dz) +
-                             c4 * (1.0 - dx) * (1.0 - dy) * dz + c5 * (1.0 - dx) * dy * dz +
-                             c6 * dx * (1.0 - dy) * dz + c7 * dx * dy * dz;
-            out[c] = (float)v;
-        }
+        for (int c = 0; c < nc; c++) out[c] = (float)s3d_trilinear_f64(src + c, sxs, sys, szs, tx, ty, tz);
     } else {
         const double a = 2.0;
         const double flx = floor(tx), fly = floor(ty), flz = floor(tz);
@@ -950,6 +954,226 @@ extern "C" int s3d_k_field_norm(const float *d_u, size_t nvox, double *d_partial
     const unsigned grid = (unsigned)(blocks < S3D_FIELD_NORM_SLOTS ? blocks : S3D_FIELD_NORM_SLOTS);
     S3D_HIP(hipMemsetAsync(d_partials, 0, (size_t)S3D_FIELD_NORM_SLOTS * 3 * sizeof(double), (hipStream_t)stream));
     hipLaunchKernelGGL(k_field_norm, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_u, nvox, d_partials);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* ---- the inverse of a displacement field and the Jacobian determinant of its map (include/s3d_device.h has the definitions) ---
+ * Both walk a volume the way k_demons_step does: workgroup g of a grid that depends on the dimensions only takes the rows g,
+ * g + G, .., 256 x-consecutive voxels at a time, keeps its statistics in registers, reduces them by shuffles and through LDS in
+ * wave order and leaves them in its own slot of d_partials, which the call has cleared; the caller adds the slots in order.
+ *
+ * k_field_invert: per source voxel the fixed-point iteration w <- -B s(B y + w), s the tri-linear sample of the field continued
+ * constantly past its faces.  The field is only read, so a voxel's iteration depends on no other voxel's and one launch runs all
+ * of them to their end; a wave stays in the loop until its slowest lane is done.  Per update: 24 gathers (eight corners of three
+ * components, of which a smooth field leaves most in the same cache lines as the neighbouring lanes') and some 130 f64
+ * operations, none of them a division. */
+struct InvStat { double n[4], k, sum, big; };
+
+__device__ __forceinline__ double s3d_wave_max_f64(double v)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_down(v, d);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double s3d_wave_min_f64(double v)
+{
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_down(v, d);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double s3d_clamp_d(double v, double hi) { return v < 0.0 ? 0.0 : v > hi ? hi : v; }
+
+__global__ void __launch_bounds__(256)
+k_field_invert(const float *__restrict__ u, int rnx, int rny, int rnz, AffineD A, AffineD B, float *__restrict__ w_out, int snx,
+               int sny, uint32_t rows, int max_iter, double tol2, unsigned char *__restrict__ status, double *__restrict__ partials)
+{
+    __shared__ double s_red[4][S3D_FIELD_INV_STATS];
+    const uint32_t tid = threadIdx.x;
+    const size_t rn = (size_t)rnx * rny * rnz, sn = (size_t)rows * snx;
+    const size_t sys = (size_t)rnx, szs = (size_t)rnx * rny;
+    const double hx = (double)(rnx - 1), hy = (double)(rny - 1), hz = (double)(rnz - 1);
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0, sum_k = 0.0, sum_res = 0.0, max_res = 0.0;
+    for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const uint32_t z = row / (uint32_t)sny, y = row - z * (uint32_t)sny;
+        for (int x0 = 0; x0 < snx; x0 += 256) {
+            const int x = x0 + (int)tid;
+            if (x >= snx) continue;
+            double p0x, p0y, p0z;
+            s3d_affine_xyz(B, (double)x, (double)y, (double)z, p0x, p0y, p0z);
+            double wx = 0.0, wy = 0.0, wz = 0.0, e2 = 0.0;
+            int k = 0, st;
+            for (;;) {
+                const double px = p0x + wx, py = p0y + wy, pz = p0z + wz;
+                if (!(s3d_finite_d(px) && s3d_finite_d(py) && s3d_finite_d(pz))) { st = 3; break; }
+                const double qx = s3d_clamp_d(px, hx), qy = s3d_clamp_d(py, hy), qz = s3d_clamp_d(pz, hz);
+                const double s0 = s3d_trilinear_f64(u, 1, sys, szs, qx, qy, qz);
+                const double s1 = s3d_trilinear_f64(u + rn, 1, sys, szs, qx, qy, qz);
+                const double s2 = s3d_trilinear_f64(u + 2 * rn, 1, sys, szs, qx, qy, qz);
+                if (!(s3d_finite_d(s0) && s3d_finite_d(s1) && s3d_finite_d(s2))) { st = 3; break; }
+                const double rx = ((A.a[0] * wx + A.a[1] * wy) + A.a[2] * wz) + s0;
+                const double ry = ((A.a[4] * wx + A.a[5] * wy) + A.a[6] * wz) + s1;
+                const double rz = ((A.a[8] * wx + A.a[9] * wy) + A.a[10] * wz) + s2;
+                e2 = (rx * rx + ry * ry) + rz * rz;
+                if (e2 <= tol2) { st = (qx == px && qy == py && qz == pz) ? 0 : 1; break; }
+                if (k == max_iter) { st = 2; break; }
+                wx = -((B.a[0] * s0 + B.a[1] * s1) + B.a[2] * s2);
+                wy = -((B.a[4] * s0 + B.a[5] * s1) + B.a[6] * s2);
+                wz = -((B.a[8] * s0 + B.a[9] * s1) + B.a[10] * s2);
+                k++;
+            }
+            const size_t i = (size_t)row * snx + x;
+            if (st == 3) {
+                s3d_u32a *wb = (s3d_u32a *)w_out;
+                wb[i] = 0x7FC00000u;
+                wb[sn + i] = 0x7FC00000u;
+                wb[2 * sn + i] = 0x7FC00000u;
+                n3 += 1.0;
+            } else {
+                w_out[i] = (float)wx;
+                w_out[sn + i] = (float)wy;
+                w_out[2 * sn + i] = (float)wz;
+                const double res = sqrt(e2);
+                sum_res += res;
+                max_res = res > max_res ? res : max_res;
+                if (st == 0) n0 += 1.0;
+                else if (st == 1) n1 += 1.0;
+                else n2 += 1.0;
+            }
+            sum_k += (double)k;
+            if (status != NULL) status[i] = (unsigned char)st;
+        }
+    }
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    const double r0 = s3d_wave_sum_f64(n0), r1 = s3d_wave_sum_f64(n1), r2 = s3d_wave_sum_f64(n2), r3 = s3d_wave_sum_f64(n3);
+    const double r4 = s3d_wave_sum_f64(sum_k), r5 = s3d_wave_sum_f64(sum_res), r6 = s3d_wave_max_f64(max_res);
+    if (lane == 0) {
+        s_red[wave][0] = r0; s_red[wave][1] = r1; s_red[wave][2] = r2; s_red[wave][3] = r3;
+        s_red[wave][4] = r4; s_red[wave][5] = r5; s_red[wave][6] = r6;
+    }
+    __syncthreads();
+    if (tid < S3D_FIELD_INV_STATS) {
+        double v;
+        if (tid == 6) {
+            v = s_red[0][6];
+            for (int w = 1; w < 4; w++) v = s_red[w][6] > v ? s_red[w][6] : v;
+        } else {
+            v = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+        }
+        partials[(size_t)blockIdx.x * S3D_FIELD_INV_STATS + tid] = v;
+    }
+}
+
+extern "C" int s3d_k_field_invert_slots(void) { return S3D_FIELD_INV_SLOTS; }
+extern "C" int s3d_k_field_invert_stats(void) { return S3D_FIELD_INV_STATS; }
+
+extern "C" int s3d_k_field_invert(const float *d_u, int rnx, int rny, int rnz, const double A[12], const double B[12], float *d_w,
+                                  int snx, int sny, int snz, int max_iter, double tol, unsigned char *d_status, double *d_partials,
+                                  s3d_stream stream)
+{
+    if (rnx < 1 || rny < 1 || rnz < 1 || snx < 1 || sny < 1 || snz < 1) S3D_FAIL("bad dimensions");
+    if (d_u == NULL || d_w == NULL || A == NULL || B == NULL || d_partials == NULL) S3D_FAIL("missing buffer");
+    if (max_iter < 0) S3D_FAIL("max_iter must not be negative");
+    if (!(tol >= 0.0)) S3D_FAIL("tol must be a number >= 0");
+    if (sny > 65535 || snz > 65535) S3D_FAIL("volume too large for the resampling grid");
+    const size_t rows = (size_t)sny * snz;
+    const unsigned grid = (unsigned)(rows < S3D_FIELD_INV_SLOTS ? rows : S3D_FIELD_INV_SLOTS);
+    AffineD a, b;
+    for (int i = 0; i < 12; i++) { a.a[i] = A[i]; b.a[i] = B[i]; }
+    S3D_HIP(hipMemsetAsync(d_partials, 0, (size_t)S3D_FIELD_INV_SLOTS * S3D_FIELD_INV_STATS * sizeof(double), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_field_invert, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_u, rnx, rny, rnz, a, b, d_w, snx, sny,
+                       (uint32_t)rows, max_iter, tol * tol, d_status, d_partials);
+    S3D_CHECK_LAUNCH();
+    return S3D_OK;
+}
+
+/* the derivative of a component along one axis at index i of n >= 2 (p: the voxel's entry, stride in floats): central inside,
+ * one-sided on the two faces */
+__device__ __forceinline__ double s3d_field_diff(const float *__restrict__ p, ptrdiff_t stride, int i, int n)
+{
+    if (i == 0) return (double)p[stride] - (double)p[0];
+    if (i == n - 1) return (double)p[0] - (double)p[-stride];
+    return ((double)p[stride] - (double)p[-stride]) * 0.5;
+}
+
+/* k_field_jacobian: 18 loads per voxel (the x neighbours are the neighbouring lanes' own entries, the y and z neighbours full
+ * rows read as such), nine differences and the 3 x 3 determinant of A + grad u. */
+__global__ void __launch_bounds__(256)
+k_field_jacobian(const float *__restrict__ u, int rnx, int rny, int rnz, uint32_t rows, AffineD A, float *__restrict__ det_out,
+                 double *__restrict__ partials)
+{
+    __shared__ double s_red[4][S3D_FIELD_JAC_STATS];
+    const uint32_t tid = threadIdx.x;
+    const size_t rn = (size_t)rows * rnx;
+    const ptrdiff_t sys = (ptrdiff_t)rnx, szs = (ptrdiff_t)rnx * rny;
+    double sum = 0.0, cnt = 0.0, fold = 0.0, lo = __builtin_huge_val(), hi = -__builtin_huge_val();
+    for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int z = (int)(row / (uint32_t)rny), y = (int)(row - (uint32_t)z * (uint32_t)rny);
+        for (int x0 = 0; x0 < rnx; x0 += 256) {
+            const int x = x0 + (int)tid;
+            if (x >= rnx) continue;
+            const size_t i = (size_t)row * rnx + x;
+            double J[9];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float *p = u + c * rn + i;
+                J[3 * c + 0] = A.a[4 * c + 0] + s3d_field_diff(p, 1, x, rnx);
+                J[3 * c + 1] = A.a[4 * c + 1] + s3d_field_diff(p, sys, y, rny);
+                J[3 * c + 2] = A.a[4 * c + 2] + s3d_field_diff(p, szs, z, rnz);
+            }
+            const double det = (J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6])) +
+                               J[2] * (J[3] * J[7] - J[4] * J[6]);
+            if (det_out != NULL) det_out[i] = (float)det;
+            if (!s3d_finite_d(det)) continue;
+            sum += det;
+            cnt += 1.0;
+            if (det <= 0.0) fold += 1.0;
+            lo = det < lo ? det : lo;
+            hi = det > hi ? det : hi;
+        }
+    }
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    const double r0 = s3d_wave_sum_f64(sum), r1 = s3d_wave_sum_f64(cnt), r2 = s3d_wave_sum_f64(fold);
+    const double r3 = s3d_wave_min_f64(lo), r4 = s3d_wave_max_f64(hi);
+    if (lane == 0) {
+        s_red[wave][0] = r0; s_red[wave][1] = r1; s_red[wave][2] = r2; s_red[wave][3] = r3; s_red[wave][4] = r4;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double *out = partials + (size_t)blockIdx.x * S3D_FIELD_JAC_STATS;
+        for (int k = 0; k < 3; k++) out[k] = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
+        double a = s_red[0][3], b = s_red[0][4];
+        for (int w = 1; w < 4; w++) {
+            a = s_red[w][3] < a ? s_red[w][3] : a;
+            b = s_red[w][4] > b ? s_red[w][4] : b;
+        }
+        out[3] = a;
+        out[4] = b;
+    }
+}
+
+extern "C" int s3d_k_field_jacobian_slots(void) { return S3D_FIELD_JAC_SLOTS; }
+extern "C" int s3d_k_field_jacobian_stats(void) { return S3D_FIELD_JAC_STATS; }
+
+extern "C" int s3d_k_field_jacobian(const float *d_u, int rnx, int rny, int rnz, const double A[12], float *d_det,
+                                    double *d_partials, s3d_stream stream)
+{
+    if (rnx < 2 || rny < 2 || rnz < 2) S3D_FAIL("every dimension must be at least 2 (a derivative needs two samples)");
+    if (d_u == NULL || A == NULL || d_partials == NULL) S3D_FAIL("missing buffer");
+    if (rny > 65535 || rnz > 65535) S3D_FAIL("volume too large for the resampling grid");
+    const size_t rows = (size_t)rny * rnz;
+    const unsigned grid = (unsigned)(rows < S3D_FIELD_JAC_SLOTS ? rows : S3D_FIELD_JAC_SLOTS);
+    AffineD a;
+    for (int i = 0; i < 12; i++) a.a[i] = A[i];
+    S3D_HIP(hipMemsetAsync(d_partials, 0, (size_t)S3D_FIELD_JAC_SLOTS * S3D_FIELD_JAC_STATS * sizeof(double), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_field_jacobian, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_u, rnx, rny, rnz, (uint32_t)rows, a,
+                       d_det, d_partials);
     S3D_CHECK_LAUNCH();
     return S3D_OK;
 }

@@ -71,6 +71,14 @@ def bind_extensions(L: C.CDLL) -> None:
         L.sift3d_amd_register_demons_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp,
                                                      P(abi.DemonsOpts), _vp, P(abi.DemonsInfo), _vp]
         L.sift3d_amd_im_warp_field.argtypes = [_vp, P(abi.Image), P(abi.Image), C.c_int, P(abi.Image)]
+    if hasattr(L, "sift3d_amd_invert_field"):             # (absent from builds older than the field inversion)
+        L.sift3d_amd_invert_field.argtypes = [_vp, P(abi.Image), C.c_int, C.c_int, C.c_int, P(C.c_double), P(abi.FieldInverseOpts),
+                                              P(abi.Affine), P(abi.Image), P(abi.FieldInverseInfo)]
+        L.sift3d_amd_invert_field_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                                  P(abi.FieldInverseOpts), P(C.c_double), P(abi.FieldInverseInfo), _vp]
+        L.sift3d_amd_field_jacobian.argtypes = [_vp, P(abi.Image), P(abi.Image), P(abi.FieldJacobianInfo)]
+        L.sift3d_amd_field_jacobian_dev.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, P(abi.FieldJacobianInfo), _vp]
+        L.sift3d_amd_field_apply_points.argtypes = [_vp, P(abi.Image), P(abi.Mat_rm), P(abi.Mat_rm)]
 
 
 class DeviceLib:
@@ -154,6 +162,11 @@ class DeviceLib:
                                           C.POINTER(C.c_double), _vp, C.c_int, _vp]
             L.s3d_k_field_upsample2.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]
             L.s3d_k_field_norm.argtypes = [_vp, C.c_size_t, _vp, _vp]
+        if hasattr(L, "s3d_k_field_invert"):              # (absent from builds older than the field inversion)
+            _dp = C.POINTER(C.c_double)
+            L.s3d_k_field_invert.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_double, _vp, _vp, _vp]
+            L.s3d_k_field_jacobian.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _vp, _vp, _vp]
         L.s3d_mesh_table.argtypes = [_f32p]
         L.s3d_mesh_table.restype = None
 
@@ -398,6 +411,50 @@ class DeviceLib:
         for v in part[:, 0]:
             total += float(v)
         return total, int(part[:, 1].sum()), float(part[:, 2].max())
+
+    def field_invert(self, d_u: int, rdims, A, B, d_w: int, sdims, max_iter: int = 30, tol: float = 1e-3,
+                     d_status: int | None = None, stream=None) -> dict:
+        """The inverse of the map A [x 1]^T + u(x) as the planar field d_w over sdims, B the inverse of A (s3d_k_field_invert;
+        d_status: one byte per source voxel or None).  Returns the statistics, the per-workgroup partials added here in slot
+        order: counts (four, by status), updates, sum_residual, max_residual."""
+        slots, stats = int(self.L.s3d_k_field_invert_slots()), int(self.L.s3d_k_field_invert_stats())
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        b = np.ascontiguousarray(B, np.float64).reshape(12)
+        dp = C.POINTER(C.c_double)
+        d_part = self.malloc(slots * stats * 8)
+        try:
+            self.check(self.L.s3d_k_field_invert(_vp(d_u), rdims[0], rdims[1], rdims[2], a.ctypes.data_as(dp), b.ctypes.data_as(dp),
+                                                 _vp(d_w), sdims[0], sdims[1], sdims[2], int(max_iter), float(tol), _vp(d_status),
+                                                 _vp(d_part), _vp(stream)), "s3d_k_field_invert")
+            part = self.download(d_part, (slots, stats), np.float64, stream)
+        finally:
+            self.free(d_part)
+        total = 0.0
+        for v in part[:, 5]:
+            total += float(v)
+        return {"counts": tuple(int(part[:, k].sum()) for k in range(4)), "updates": int(part[:, 4].sum()),
+                "sum_residual": total, "max_residual": float(part[:, 6].max())}
+
+    def field_jacobian(self, d_u: int, rdims, A, d_det: int | None = None, stream=None) -> dict:
+        """det(A's linear part + grad u) per voxel of the planar field d_u to d_det (float32, or None: statistics only) --
+        s3d_k_field_jacobian.  Returns the statistics over the finite determinants, the partials added here in slot order: sum,
+        n_finite, n_folded (those <= 0), min, max (NaN when none is finite)."""
+        slots, stats = int(self.L.s3d_k_field_jacobian_slots()), int(self.L.s3d_k_field_jacobian_stats())
+        a = np.ascontiguousarray(A, np.float64).reshape(12)
+        d_part = self.malloc(slots * stats * 8)
+        try:
+            self.check(self.L.s3d_k_field_jacobian(_vp(d_u), rdims[0], rdims[1], rdims[2], a.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   _vp(d_det), _vp(d_part), _vp(stream)), "s3d_k_field_jacobian")
+            part = self.download(d_part, (slots, stats), np.float64, stream)
+        finally:
+            self.free(d_part)
+        used = part[part[:, 1] > 0]
+        total = 0.0
+        for v in used[:, 0]:
+            total += float(v)
+        return {"sum": total, "n_finite": int(used[:, 1].sum()), "n_folded": int(used[:, 2].sum()),
+                "min": float(used[:, 3].min()) if len(used) else float("nan"),
+                "max": float(used[:, 4].max()) if len(used) else float("nan")}
 
     def mesh_table(self) -> np.ndarray:
         out = np.zeros(20 * 16 + 32, np.float32)      # S3D_MESH_FLOATS: face table + 32-word face LUT
